@@ -19,9 +19,12 @@ Other workloads (rows of BASELINE.json `configs`; never the default line):
                   features computed once, encoder passes of 4 clips x 64 captions = 256 pairs); N > 1 shards the videos over the ranks and
                   gathers the (vid, txt, score) rows once at the end (inside the timed region)
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel family of the step (bf16 MFMA GEMM /
-implicit-GEMM conv), timed live with HIP events on the launch stream; `cpu_baseline` is the CPU oracle
-(oracle/clipbert_oracle.py, a port of the reference arithmetic in stock PyTorch fp32 ops) on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints the line; `--dump-outputs DIR`
+then also writes what the last timed step computed (DIR/<name>.npy, float32 / float64, a fixed seeded sample of the parameters).
+Everything else is measured or checked only with `--full`: `roofline` describes the dominant kernel family of the step (bf16 MFMA
+GEMM / implicit-GEMM conv), timed live with HIP events on the launch stream; `cpu_baseline` is the CPU oracle
+(oracle/clipbert_oracle.py, a port of the reference arithmetic in stock PyTorch fp32 ops) on a bounded sample; N > 1 adds the
+cross-rank parameter check and the exposed-communication estimate.
 """
 import argparse
 import json
@@ -71,6 +74,9 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--forward-only", action="store_true", help="diagnostic: forward of the training batch only (not the reported metric)")
+    ap.add_argument("--full", action="store_true", help="also the measurements and checks beside the headline figure: roofline, CPU baseline, "
+                    "N > 1 parameter self-check and exposed communication")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     a = ap.parse_args()
     for k, v in MODES[a.mode].items():
         if k != "head" and getattr(a, k, None) is None:
@@ -285,7 +291,7 @@ def main():
     torch.cuda.synchronize()
     log("eager warm-up done" + (f", loss {float(loss.item()):.4f}" if loss is not None else ""))
     dp_check = None
-    if train and world > 1:
+    if train and world > 1 and args.full:
         dp_check = dp_self_check(bank, dist, dev, compute_weights=sync.shard)
         log(f"DP self-check: {dp_check}")
 
@@ -470,8 +476,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        run()
+        last = run()
     if flush_pipeline is not None:
         flush_pipeline()                                   # (inside the timed region: every step's whole update is paid for)
     gathered = None
@@ -490,6 +497,11 @@ def main():
     value = clips_per_step / (elapsed / args.steps)
     final_loss = float(loss.item()) if loss is not None else None
     log(f"timed region done: {ms_per_step:.3f} ms/step, {value:.1f} clips/s")
+    if args.dump_outputs and rank == 0:
+        step_loss = last if torch.is_tensor(last) else loss
+        dump_outputs(args.dump_outputs, loss=step_loss, bank=bank if train else None,
+                      scores=[r["score"] for r in infer_rows[-rep:]] if args.mode == "infer16" else None)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     pairs = bv * rep * nclip
     if args.mode == "train" and not args.forward_only:
@@ -541,7 +553,7 @@ def main():
     # link time the plan failed to hide.  The ranks' parameters diverge from here on -- nothing after this uses them.  The measured
     # line is COMPLETE before this starts: if the diagnostic hangs (it re-captures the step), a watchdog prints the line without it,
     # marks the attempt done and exits -- a diagnostic must never cost the measurement.
-    if train and world > 1 and sync is not None and sync.active and not sync.dry and os.environ.get("CB_BENCH_EXPOSED", "1") != "0":
+    if args.full and train and world > 1 and sync is not None and sync.active and not sync.dry and os.environ.get("CB_BENCH_EXPOSED", "1") != "0":
         import threading
 
         def bail():
@@ -576,11 +588,11 @@ def main():
         except Exception as e:                                  # noqa: BLE001
             out["config"]["exposed_comm"] = {"error": repr(e)[:200]}
         timer.cancel()
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline:
         default_shape = args.mode == "train" and (nclip, T, args.size, args.txt_len, bv, rep) == (2, 2, 224, 32, 16, 2) and not args.forward_only
         out["roofline"] = measure_roofline(eager_fn if args.mode != "infer16" else infer_device_step, pmc_ok=default_shape, ms_per_step=ms_per_step)
         log("roofline measured")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, args)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -594,6 +606,29 @@ def main():
             sys.stdout.flush()
             sys.stderr.flush()
             os._exit(0)
+
+
+DUMP_PARAM_SAMPLE = 1 << 22                # fp32 parameters written by --dump-outputs: 16 MB
+
+
+def dump_outputs(path, loss=None, bank=None, scores=None):
+    """--dump-outputs: what the last timed step computed, for output-for-output comparison of two builds on the same arguments.
+    loss.npy: the step's loss (float32); params.npy: the fp32 master parameters after the step's update, at DUMP_PARAM_SAMPLE
+    positions drawn with a fixed seed (the same positions on every run of the same model); scores.npy (infer16): the last step's
+    retrieval scores (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if loss is not None:
+        np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
+    if bank is not None:
+        n = bank.master.numel()
+        if n <= DUMP_PARAM_SAMPLE:
+            idx = torch.arange(n)
+        else:
+            idx = torch.randint(0, n, (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(1234)).unique()
+        np.save(os.path.join(path, "params.npy"), bank.master[idx.to(bank.master.device)].float().cpu().numpy())
+    if scores is not None:
+        np.save(os.path.join(path, "scores.npy"), np.asarray(scores, dtype=np.float64))
 
 
 def rccl_summary():

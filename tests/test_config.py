@@ -8,8 +8,9 @@ import torch
 
 from clipbert_amd import config as C
 
-REF_CFG = "/root/reference/src/configs"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="needs /root/reference")
+# the reference's own task / model config files, stored verbatim as fixtures in the reference's layout (src/configs/...)
+REF_ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_configs")
+REF_CFG = os.path.join(REF_ROOT, "src", "configs")
 
 
 def test_config_attribute_access_and_nesting():
@@ -21,7 +22,6 @@ def test_config_attribute_access_and_nesting():
         c.missing
 
 
-@needs_ref
 @pytest.mark.parametrize("fname,task,expect", [
     ("msrvtt_ret_base_resnet50.json", "video_retrieval", dict(num_labels=2, score_agg_func="lse", train_n_clips=8, num_frm=2, max_txt_len=20)),
     ("tgif_qa_action_base_resnet50.json", "video_qa", dict(num_labels=5)),
@@ -35,7 +35,7 @@ def test_reference_json_files_load(fname, task, expect):
     for k, v in expect.items():
         assert cfg[k] == v, (k, cfg[k])
     assert cfg.cnn_lr_mul_prefix == "grid_encoder" and cfg.warmup_ratio == 0.1          # argparse defaults fill the rest
-    mc = C.build_model_config(cfg, config_root="/root/reference")
+    mc = C.build_model_config(cfg, config_root=REF_ROOT)
     assert mc.hidden_size == 768 and mc.num_hidden_layers == 12 and mc.vocab_size == 30522 and mc.layer_norm_eps == 1e-12
     if task == "video_retrieval":
         assert (mc.num_labels, mc.loss_type, mc.classifier, mc.cls_hidden_scale) == (2, "ce", "mlp", 2)

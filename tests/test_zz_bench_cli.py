@@ -28,6 +28,34 @@ def test_default_workload_is_the_metric_configuration(monkeypatch):
     assert (c.head, c.n_clips, c.repeat, c.txt_len) == ("multiple_choice", 2, 5, 25)
 
 
+def test_full_is_off_by_default_and_dump_outputs_writes_float_arrays(monkeypatch, tmp_path):
+    """A plain run measures only the headline figure (`--full` adds the rest); `--dump-outputs DIR` writes the last timed step's loss,
+    a fixed seeded sample of the updated parameters and (infer16) the scores as float32 / float64 .npy files."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    from types import SimpleNamespace
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path)
+    master = torch.randn(1000)
+    bench.dump_outputs(str(tmp_path / "small"), loss=torch.tensor(0.25), bank=SimpleNamespace(master=master), scores=[0.5, 0.125])
+    assert np.load(tmp_path / "small" / "loss.npy").tolist() == [0.25]
+    assert np.array_equal(np.load(tmp_path / "small" / "params.npy"), master.numpy())
+    sc = np.load(tmp_path / "small" / "scores.npy")
+    assert sc.dtype == np.float64 and sc.tolist() == [0.5, 0.125]
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 64)                     # larger than the sample: the same seeded positions every time
+    for d in ("big0", "big1"):
+        bench.dump_outputs(str(tmp_path / d), bank=SimpleNamespace(master=master))
+    p0, p1 = np.load(tmp_path / "big0" / "params.npy"), np.load(tmp_path / "big1" / "params.npy")
+    assert p0.dtype == np.float32 and 0 < p0.size <= 64 and np.array_equal(p0, p1)
+    assert np.isin(p0, master.numpy()).all() and not (tmp_path / "big0" / "loss.npy").exists()
+
+
 def test_supervisor_retries_with_the_next_plan_and_honours_the_done_marker(monkeypatch, tmp_path):
     """bench.py's N > 1 supervisor: a failed attempt is retried with the next, more conservative plan; a hung one is
     killed at the deadline; an attempt that completed its timed region and JSON line (done marker) but died in teardown counts as done."""
@@ -133,7 +161,7 @@ def test_two_rank_dry_run_on_one_gpu(mode):
     # retry after a hung attempt inside this test's own limit)
     env = dict(os.environ, CB_BENCH_SHARE_GPU="1", CB_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", CB_BENCH_ATTEMPT_TIMEOUT="330")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mode", mode]
+           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mode", mode, "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -155,7 +183,7 @@ def test_bare_gpus_2_launches_its_own_ranks():
     env = dict(os.environ, CB_BENCH_SHARE_GPU="1", CB_BENCH_BACKEND="gloo", CB_BENCH_ATTEMPT_TIMEOUT="330")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "CB_BENCH_WORKER"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"], env=env, capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], env=env, capture_output=True,
                        text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -169,7 +197,7 @@ def _multi_gpu_bench(extra_env, n=2):
     env = dict(os.environ, **extra_env)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "CB_BENCH_WORKER"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1"], env=env, capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3", "--warmup", "1", "--full"], env=env, capture_output=True,
                        text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -228,3 +256,26 @@ def test_loopback_owner_only_update_is_captured_and_trains():
     cfg = out["config"]
     assert cfg["n_graphs"] == 1 and cfg["update"].startswith("owner-only") and "cb_reduce_scatter_bucket" in cfg["grad_exchange"]
     assert out["value"] > 0 and 0.0 < cfg["final_loss"] < 5.0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_given_steps_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR`: exactly the headline line (no roofline / CPU baseline without
+    `--full`), `steps` and `ms_per_step` of the N timed steps, and the last step's outputs as finite float arrays within 64 MB."""
+    import numpy as np
+    out_dir = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert (out["unit"], out["higher_is_better"], out["dtype"]) == ("clips/s", True, "bf16")
+    assert "roofline" not in out and "cpu_baseline" not in out
+    files = sorted(p.name for p in out_dir.iterdir())
+    assert files == ["loss.npy", "params.npy"], files
+    assert sum(p.stat().st_size for p in out_dir.iterdir()) <= 64 << 20
+    for name in files:
+        arr = np.load(out_dir / name)
+        assert arr.dtype in (np.float32, np.float64) and arr.size > 0 and np.isfinite(arr).all(), name
