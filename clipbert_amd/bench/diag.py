@@ -34,9 +34,8 @@ def build(ctx):
         with torch.cuda.stream(pipe_stream):
             opt.launch(groups=T_GROUPS, prev=True, reuse_norm=True)          # step i-1's transformer update (no-op before the first step)
             bank.zero_grad_range(0, t_end, lazy=True)                        # ... then its gradients may go
-        bank.grad_epoch = getattr(bank, "grad_epoch", 0) + 1
+        bank.begin_epoch(lazy=True)                                          # (the lazy span is written by this step's encoder backward)
         bank.zero_grad_range(t_end, bank.grad.numel())
-        bank.lazy_fresh = bank.lazy_span is not None
         model.rt.pending_encoder_nodes = model.rt.pending_cnn_nodes = 0
         vis = frames.view(bv * nclip, T, *frames.shape[2:]) if (fold and nclip > 1) else frames
         grid = model.grid_features(vis)                                      # ResNet forward beside the deferred update

@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(1024) sum_two_final_kernel(const float* a, int
         float t = 0.f;
 #pragma unroll
         for (int w = 0; w < 16; ++w) t += red[w];
-        out[0] += t;
+        out[0] = t;
     }
 }
 

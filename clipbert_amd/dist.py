@@ -210,7 +210,7 @@ class GradSync:
         if self.world > 1 or self.loopback or self.dry:
             # the gradient norm of a data-parallel step is the norm of the EXCHANGED gradients: the per-launch shares of the local ones
             # (ParamBank.enable_norm_fold) say nothing about it -- FusedAdamW.launch runs its pass over the reduced gradients
-            bank.norm_fold_blocked = True
+            bank.block_norm_fold()
         t_end = bank.group_range[3][1]
         self.t_range = (0, t_end)
         self.c_range = (t_end, bank.n_train)
@@ -238,7 +238,7 @@ class GradSync:
         self._buckets_done: List = []
         self._owned: List = []              # (lo, hi) pieces of the flat buffers this rank owns, from the buckets reduced since wait()
         self._buckets: List = []            # (s, e) of every bucket of the current exchange
-        self._epoch_done = getattr(bank, "grad_epoch", 0)    # bank.grad_epoch (one per zero_grad) of the last completed exchange
+        self._epoch_done = bank.grad_epoch  # bank.grad_epoch (one per zero_grad) of the last completed exchange
         self._grid = None                   # bucket_grid(): fixed at first use
         self._grid_used = False
         want_native = comm == "native" or (comm == "auto" and dist.is_initialized() and bank.grad.is_cuda and dist.get_backend(group) == "nccl")
@@ -270,6 +270,7 @@ class GradSync:
         if not self.active or b <= a or self.compress != "bf16":
             return
         from . import ops
+        self.bank.finish(a, b)
         self._ensure_wire()
         if self.bank.grad.is_cuda:
             ops.cast(self.bank.grad[a:b], self._wire[a:b])
@@ -366,6 +367,7 @@ class GradSync:
                                f"{sorted({x for r in [self.t_range, self.c_range] + list(self.c_early) for x in r})}): reduce the transformer / CNN ranges "
                                "(or their set_cnn_split parts), not arbitrary slices")
         self._grid_used = True
+        self.bank.finish(a, b)                                 # (first-writer gradients a partial backward never wrote: zeros, not garbage)
         for s, e in buckets:
             if self.shard:
                 assert (e - s) % (64 * self.world) == 0, "shard=True: ranges must start / end at multiples of world x 64 elements (ParamBank.GROUP_ALIGN)"
@@ -458,7 +460,7 @@ class GradSync:
             if self.native is not None:
                 torch.cuda.current_stream(bank.grad.device).wait_stream(self.comm_stream)
         if optimizer is not None or not self.active:
-            bank.owner_only_dirty = False
+            bank.set_owner_only_dirty(False)
 
     def _gather(self, t: torch.Tensor):
         if self.mute:
@@ -516,7 +518,7 @@ class GradSync:
         # leave part of the gradient buffer un-exchanged -- whatever is missing goes out now, late but correct
         # -- including a step for which NO reduce_* was called at all (hooks not armed, caller forgot): the gradient epoch of the
         # bank (one per zero_grad) tells that case from a repeated wait() with nothing left to do
-        epoch = getattr(self.bank, "grad_epoch", 0)
+        epoch = self.bank.grad_epoch
         if self.active and (self._inflight or epoch != self._epoch_done):
             for a, b in self._uncovered():
                 self.late_ranges += 1

@@ -15,9 +15,7 @@ sums, ReLU/FrozenBN masks and bias/LayerNorm reductions are fused into kernel ep
 being left to autograd's eager tensor ops.  Parameter gradients are accumulated by the kernels
 directly into the flat fp32 gradient buffer (``p.grad`` is a view of it).
 """
-import contextlib
 import math
-import os
 from types import SimpleNamespace
 from typing import List, Optional
 
@@ -28,7 +26,6 @@ from torch import nn
 from . import ops
 from .ops import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_TANH, KROW, KROW_GATHER, KROW_TAPS, ROWK, ROWK_GATHER)
 
-_GELU_SAVE_GRAD = os.environ.get("CB_NO_GELU_SAVE_GRAD") is None      # FFN1 stores gelu'(pre) for the backward instead of the pre-activation
 from .params import ParamBank
 
 FROZEN_BN_EPS = 1e-5
@@ -164,23 +161,6 @@ class _GridConv(nn.Module):
         return None, None
 
 
-class _SideStream:
-    """torch.cuda.stream(side) + the K-split scratch of the launches inside: the side stream's own (``ws``: partial products and
-    arrival tickets belong to ONE stream, include/clipbert_hip.h) or none (the default scratch belongs to the main stream's launches)"""
-    def __init__(self, stream, ws=None):
-        self.ctx = torch.cuda.stream(stream)
-        self.ws = ws
-
-    def __enter__(self):
-        self.prev = (ops._SPLITK_OFF, ops._SPLITK_SIDE)
-        ops._SPLITK_OFF, ops._SPLITK_SIDE = self.ws is None, self.ws
-        return self.ctx.__enter__()
-
-    def __exit__(self, *exc):
-        ops._SPLITK_OFF, ops._SPLITK_SIDE = self.prev
-        return self.ctx.__exit__(*exc)
-
-
 # =================================================================================================
 # execution context shared by all modules of one ClipBert instance
 # =================================================================================================
@@ -203,37 +183,6 @@ class Runtime:
         self._ln_off = None                              # (bank, offsets of the encoder LayerNorm gradients): cache of _ln_offsets
         self.forward_count = 0                           # host counter folded into every dropout seed: each forward (each
                                                          # clip of a clip loop) draws its own masks; kept in the saved pack
-        self.side_stream = None                          # second HIP stream: weight-gradient GEMMs run beside the dgrad chain
-        self.side_ws = None                              # its own K-split scratch (ops.new_splitk_workspace)
-        self.overlap = 0                                 # what runs there (prepare(overlap_wgrad=...)): bit 0 the encoder's batched weight
-                                                         # gradients beside the ResNet backward, bit 1 a ResNet stage's grouped weight
-                                                         # gradients beside the next stage's data gradients, bit 2 every convolution's
-                                                         # weight gradient on its own (the round-1 form), bit 3 the encoder's four batched
-                                                         # weight-gradient launches on four concurrent branches (each one's last wave of
-                                                         # tiles filled by the next one's first)
-        self.fan_streams = []                            # bit 3: three more streams (the fourth branch is the issuing stream)
-        self.group_wgrads = os.environ.get("CB_NO_GROUP_WGRAD") is None     # ResNet weight gradients per stage through cb_gemm_group
-        self.group_enc_wgrads = os.environ.get("CB_NO_GROUP_ENC_WGRAD") is None   # the encoder's four batched weight-gradient kinds in one grouped launch
-        self.group_fwd_pairs = os.environ.get("CB_GROUP_FWD_PAIRS", "0") == "1"   # shortcut + conv1 of the strided stage entries in one launch: measured SLOWER (profiles/r04f: +0.1 ms; the grouped gather kernel runs the pair in 106 us against 47 + 24 apart) -- kept as a switch
-        self._side_refs = []
-
-    def side(self, *tensors):
-        """Context manager: run the enclosed launches on the side stream, ordered after everything issued so far on
-        the current stream.  The weight-gradient GEMMs of the backward pass are independent of the data-gradient
-        chain and each fills well under one block per CU, so the two streams overlap on the chip.  `tensors` are
-        kept alive until join() so the caching allocator cannot hand their memory out while the side stream reads it."""
-        if self.side_stream is None:
-            return contextlib.nullcontext()
-        ev = torch.cuda.Event()
-        ev.record()
-        self.side_stream.wait_event(ev)
-        self._side_refs.extend(tensors)
-        return _SideStream(self.side_stream, self.side_ws)
-
-    def join(self):
-        if self.side_stream is not None:
-            torch.cuda.current_stream().wait_stream(self.side_stream)
-            self._side_refs.clear()
 
     def table(self, n, oh, ow, stride, pad, sN, sH, sW, device):
         key = (n, oh, ow, stride, pad, sN, sH, sW, str(device))
@@ -269,9 +218,7 @@ def _pick_split(mo, no, kred):
 # =================================================================================================
 # CNN trunk: explicit forward / backward
 # =================================================================================================
-def _conv_fwd(rt: Runtime, x, conv, act=ACT_NONE, residual=None, relu_after=False, pending=None):
-    """``pending`` (a list): the launch is only DESCRIBED and appended; the caller hands independent convolutions of one input to
-    cb_gemm_group together (projection shortcut + conv1 of a stage-entry block)."""
+def _conv_fwd(rt: Runtime, x, conv, act=ACT_NONE, residual=None, relu_after=False):
     n, h, w, cin = x.shape
     k, s, p = conv.k, conv.stride, conv.pad
     oh, ow = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
@@ -281,15 +228,14 @@ def _conv_fwd(rt: Runtime, x, conv, act=ACT_NONE, residual=None, relu_after=Fals
     wk = rt.bank.compute(conv.weight).view(cout, k * k * cin)
     scale, shift = conv.scale_shift()
     res2d = residual.view(m, cout) if residual is not None else None
-    run = ops.gemm if pending is None else (lambda *a, **kw: pending.append(ops.gemm_desc(*a, **kw)))
     if k == 1 and s == 1:
-        run(x.view(m, cin), wk, m, cout, cin, out=y.view(m, cout), scale=scale, shift=shift, act=act,
-            residual=res2d, relu_after=relu_after)
+        ops.gemm(x.view(m, cin), wk, m, cout, cin, out=y.view(m, cout), scale=scale, shift=shift, act=act,
+                 residual=res2d, relu_after=relu_after)
     else:
         tab = rt.table(n, oh, ow, s, p, h * w * cin, w * cin, cin, x.device)
-        run(x, wk, m, cout, k * k * cin, out=y.view(m, cout), a_mode=ROWK_GATHER, a_tab=tab, lda=0,
-            ldb=k * k * cin, R=k, S=k, Cin=cin, H=h, W=w, sH=w * cin, sW=cin, scale=scale, shift=shift, act=act,
-            residual=res2d, relu_after=relu_after)
+        ops.gemm(x, wk, m, cout, k * k * cin, out=y.view(m, cout), a_mode=ROWK_GATHER, a_tab=tab, lda=0,
+                 ldb=k * k * cin, R=k, S=k, Cin=cin, H=h, W=w, sH=w * cin, sW=cin, scale=scale, shift=shift, act=act,
+                 residual=res2d, relu_after=relu_after)
     return y
 
 
@@ -359,9 +305,7 @@ def _conv_wgrad(rt: Runtime, g, x, conv, pending=None):
             ops.zero_(gw)                            # (a form the first-writer store does not cover: zero now, accumulate as ever)
     else:
         bank.fold_invalidate()
-    # (descriptors that will be LAUNCHED on the side stream carry its scratch, whichever stream describes them)
-    side_ws = rt.side_ws if (pending is not None and rt.overlap & 2) else None
-    run = ops.gemm if pending is None else (lambda *a, **kw: pending.append(ops.gemm_desc(*a, splitk_ws=side_ws, **kw)))
+    run = ops.gemm if pending is None else (lambda *a, **kw: pending.append(ops.gemm_desc(*a, **kw)))
     if k == 1 and s == 1:
         run(g.view(m, cout), x.view(m, cin), cout, cin, m, out=gw.view(cout, kk), a_mode=KROW, lda=cout,
             b_mode=KROW, ldb=cin, accumulate=acc, split_k=split, tile=tile, sq_slots=slots)
@@ -396,8 +340,8 @@ def _res2_block_fused(rt: Runtime, x, blk: BottleneckBlock):
 
 def _res2_fusable(rt: Runtime, x, blk: BottleneckBlock, save: bool) -> bool:
     """the fused forward kernel covers the frozen 64-mid-channel, stride-1 blocks in bf16 (FREEZE_AT = 2: nothing of res2 is saved for a
-    backward); CB_NO_RES2_FUSE=1 restores the three / four cb_gemm launches"""
-    if rt.dtype != torch.bfloat16 or os.environ.get("CB_NO_RES2_FUSE") is not None:
+    backward)"""
+    if rt.dtype != torch.bfloat16:
         return False
     if save and _block_trainable(rt, blk):
         return False
@@ -419,22 +363,19 @@ def cnn_forward(bb: "GridFeatBackbone", x5: torch.Tensor, save: bool):
     oh, ow = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
     m = n * oh * ow
     scale, shift = stem.scale_shift()
-    fuse_stem = rt.dtype == torch.bfloat16 and w % 2 == 0 and os.environ.get("CB_NO_STEM_FUSE") is None
-    packed = None
-    if x4.dtype == torch.uint8 and fuse_stem and os.environ.get("CB_NO_STEM_U8") is None:
+    fuse_stem = rt.dtype == torch.bfloat16 and w % 2 == 0
+    if x4.dtype == torch.uint8 and fuse_stem:
         # uint8 frames straight into the first convolution: ImageNorm, BGR flip and padding inside cb_stem_pool's tile loader (round 6, N4)
         x = ops.stem_pool_u8(x4, bb.pixel_mean, bb.pixel_std, _stem_weight(rt, stem), scale, shift)
-    elif x4.dtype == torch.uint8:
-        packed = ops.stem_pack(x4, rt.dtype, 3, bb.pixel_mean, bb.pixel_std, extra_w=2)
-    else:
-        packed = ops.stem_pack(x4.float(), rt.dtype, 3, extra_w=2)
-    hp, wp = (packed.shape[1], packed.shape[2]) if packed is not None else (0, 0)
-    if packed is None:
-        pass
     elif fuse_stem:
-        # convolution + FrozenBN + ReLU + max-pool in one launch (the 112 x 112 x 64 map never leaves the CU); CB_NO_STEM_FUSE=1: two launches
-        x = ops.stem_pool(packed, _stem_weight(rt, stem), scale, shift, oh, ow)
+        # convolution + FrozenBN + ReLU + max-pool in one launch (the 112 x 112 x 64 map never leaves the CU)
+        x = ops.stem_pool(ops.stem_pack(x4.float(), rt.dtype, 3, extra_w=2), _stem_weight(rt, stem), scale, shift, oh, ow)
     else:
+        if x4.dtype == torch.uint8:
+            packed = ops.stem_pack(x4, rt.dtype, 3, bb.pixel_mean, bb.pixel_std, extra_w=2)
+        else:
+            packed = ops.stem_pack(x4.float(), rt.dtype, 3, extra_w=2)
+        hp, wp = packed.shape[1], packed.shape[2]
         tab = rt.table(n, oh, ow, 2, 0, hp * wp * 4, wp * 4, 4, x5.device)
         y = torch.empty(n, oh, ow, 64, dtype=rt.dtype, device=x5.device)
         ops.gemm(packed, _stem_weight(rt, stem), m, 64, 224, out=y.view(m, 64), a_mode=ROWK_GATHER, a_tab=tab, lda=0, ldb=224,
@@ -446,16 +387,8 @@ def cnn_forward(bb: "GridFeatBackbone", x5: torch.Tensor, save: bool):
             if _res2_fusable(rt, x, blk, save):
                 x = _res2_block_fused(rt, x, blk)
                 continue
-            if blk.shortcut is not None and blk.conv1.stride > 1 and rt.group_fwd_pairs:
-                # stage entry with a stride: projection shortcut and conv1 read the same strided pixels -- one grouped launch
-                # (the stride-1 entry of res2 stays two launches: its shortcut is a streaming-kernel shape, cb_gemm tile 8)
-                pair = []
-                sc = _conv_fwd(rt, x, blk.shortcut, pending=pair)
-                y1 = _conv_fwd(rt, x, blk.conv1, act=ACT_RELU, pending=pair)
-                ops.gemm_group(pair, x)
-            else:
-                sc = _conv_fwd(rt, x, blk.shortcut) if blk.shortcut is not None else x
-                y1 = _conv_fwd(rt, x, blk.conv1, act=ACT_RELU)
+            sc = _conv_fwd(rt, x, blk.shortcut) if blk.shortcut is not None else x
+            y1 = _conv_fwd(rt, x, blk.conv1, act=ACT_RELU)
             y2 = _conv_fwd(rt, y1, blk.conv2, act=ACT_RELU)
             out = _conv_fwd(rt, y2, blk.conv3, residual=sc, relu_after=True)
             if save and _block_trainable(rt, blk):
@@ -487,27 +420,19 @@ def cnn_backward_steps(bb: "GridFeatBackbone", saved_pack, dgrid: torch.Tensor):
     saved, res5, gy, grid = saved_pack
     gconv = bb.grid_encoder[0]
     dg = ops.maxpool2_bwd(gy, grid, dgrid.reshape(grid.shape).contiguous(), relu=True)
-    with (rt.side(dg, res5) if rt.overlap & 6 else contextlib.nullcontext()):
-        _conv_wgrad(rt, dg, res5, gconv)
+    _conv_wgrad(rt, dg, res5, gconv)
     if not saved:
-        rt.join()
         return
     res5_ids = {id(b) for b in bb.feature.backbone.res5}
     first_res5 = min((i for i, rec in enumerate(saved) if id(rec[0]) in res5_ids), default=None)
     # weight gradients of a stage's convolutions: described as the data-gradient chain passes them, launched together when the chain
-    # leaves the stage (cb_gemm_group; not with the side-stream variant, which overlaps them one by one)
+    # leaves the stage (cb_gemm_group)
     stage_of = {id(b): name for name, *_ in RESNET50_STAGES for b in getattr(bb.feature.backbone, name)}
-    pend = [] if (rt.group_wgrads and not rt.overlap & 4) else None
-    conv_side = rt.side if pend is None else (lambda *t: contextlib.nullcontext())     # (pending: only described here, launched by flush)
+    pend = []
 
     def flush():
-        if pend:
-            if rt.overlap & 2:                          # the stage's grouped launches beside the next stage's data gradients
-                with rt.side(*pend):                    # (the descriptors keep their operands alive until join())
-                    ops.gemm_group(pend, dg)
-            else:
-                ops.gemm_group(pend, dg)
-            pend.clear()
+        ops.gemm_group(pend, dg)
+        pend.clear()
 
     def fuse_spec(i):
         """the ReLU x FrozenBN-scale backward of block i, done by the launch that produces d(output of block i)"""
@@ -524,20 +449,16 @@ def cnn_backward_steps(bb: "GridFeatBackbone", saved_pack, dgrid: torch.Tensor):
         s2, _ = blk.conv2.scale_shift()
         s1, _ = blk.conv1.scale_shift()
         dz, gsc = (sec, None) if blk.shortcut is None else (None, sec)
-        with conv_side(g3, y2, sec):
-            _conv_wgrad(rt, g3, y2, blk.conv3, pend)
-            if blk.shortcut is not None:
-                _conv_wgrad(rt, gsc, x, blk.shortcut, pend)
+        _conv_wgrad(rt, g3, y2, blk.conv3, pend)
+        if blk.shortcut is not None:
+            _conv_wgrad(rt, gsc, x, blk.shortcut, pend)
         g2 = _conv_dgrad(rt, g3, blk.conv3, y2.shape, scale=s2, mask=y2)       # -> d(conv2 out) * mask * scale2
-        with conv_side(g2, y1):
-            _conv_wgrad(rt, g2, y1, blk.conv2, pend)
+        _conv_wgrad(rt, g2, y1, blk.conv2, pend)
         g1 = _conv_dgrad(rt, g2, blk.conv2, y1.shape, scale=s1, mask=y1)
-        with conv_side(g1, x):
-            _conv_wgrad(rt, g1, x, blk.conv1, pend)
+        _conv_wgrad(rt, g1, x, blk.conv1, pend)
         if idx == 0 or stage_of.get(id(saved[idx - 1][0])) != stage_of.get(id(blk)):
             flush()                                     # the chain leaves this stage: its weight gradients in a few grouped launches
         if idx == first_res5 and idx > 0:
-            rt.join()
             yield "grid_encoder+res5"
         if need_dx:
             spec = fuse_spec(idx - 1)
@@ -546,7 +467,6 @@ def cnn_backward_steps(bb: "GridFeatBackbone", saved_pack, dgrid: torch.Tensor):
             else:
                 dout = _conv_dgrad(rt, g1, blk.conv1, x.shape)
                 g3, sec = _conv_dgrad(rt, gsc, blk.shortcut, x.shape, out=dout, accumulate=True, fuse=spec)
-    rt.join()
 
 
 class _CnnFn(torch.autograd.Function):
@@ -785,11 +705,11 @@ def encoder_forward(model: ClipBertBaseModel, grid, ids, mask, src_row, pooled_d
         a, mean1, rstd1 = ops.layernorm_fwd(a_pre, so.LayerNorm.weight, so.LayerNorm.bias, eps, save_stats=save,
                                             out=stk.a[li] if save else None)
         hact = stk.hact[li] if save else torch.empty(M, ff, dtype=dt, device=dev)
-        hsave = torch.empty(M, ff, dtype=dt, device=dev) if save else None     # gelu'(pre) (pack.gelu_saved_grad) or the pre-activation
+        hsave = torch.empty(M, ff, dtype=dt, device=dev) if save else None     # gelu'(pre), for the backward
         # (training: the second output is gelu'(pre-activation), all the backward needs of it -- one evaluation of exp / erfc for both, and
         # the FFN2 data-gradient epilogue multiplies by the stored value instead of evaluating the derivative: CB_ACT_GELU_SAVE_GRAD)
         ops.gemm(a, bank.compute(it.dense.weight), M, ff, d, out=hact, shift=it.dense.bias,
-                 act=ops.ACT_GELU_SAVE_GRAD if (save and _GELU_SAVE_GRAD) else ACT_GELU, out2=hsave)
+                 act=ops.ACT_GELU_SAVE_GRAD if save else ACT_GELU, out2=hsave)
         o_pre = torch.empty(M, d, dtype=dt, device=dev)
         ops.gemm(hact, bank.compute(ou.dense.weight), M, d, ff, out=o_pre, shift=ou.dense.bias, residual=a, dropout_p=p_h,
                  dropout_seed=_seed(_SITE_OUT, li, fwd_i), seed_ptr=rt.seed_dev)
@@ -812,8 +732,7 @@ def encoder_forward(model: ClipBertBaseModel, grid, ids, mask, src_row, pooled_d
     if save:
         pack = SimpleNamespace(layers=layers, x_final=x, pooled=pooled, pooled_raw=pooled_raw, p_pool=p_pool, pre=pre,
                                mean0=mean0, rstd0=rstd0, ids=ids_c, key_mask=key_mask, src_row=src_row, sel=sel, bsz=bsz,
-                               lt=lt, lv=lv, L=L, grid_shape=tuple(grid.shape), p_h=p_h, p_a=p_a, stk=stk, fwd_i=fwd_i, text_repeat=text_repeat,
-                               gelu_saved_grad=bool(_GELU_SAVE_GRAD))
+                               lt=lt, lv=lv, L=L, grid_shape=tuple(grid.shape), p_h=p_h, p_a=p_a, stk=stk, fwd_i=fwd_i, text_repeat=text_repeat)
     return x, pooled, pack
 
 
@@ -880,7 +799,7 @@ def _encoder_wgrads(model, pk, gs, M):
         fresh = False
     if not fresh:
         bank.fold_invalidate()                       # (a second backward of the step accumulates: the first one's norm shares are void)
-    if all_batched and rt.group_enc_wgrads and rt.dtype == torch.bfloat16:
+    if all_batched and rt.dtype == torch.bfloat16:
         # all four kinds in ONE grouped launch (cb_gemm_group's row-sum / strided-batch class): 48 problems' 5184 tiles of 128x128 share a
         # grid, so only one last wave of tiles runs on a part-filled chip instead of four (profiles/r06k_enc_wgrad_group_ab.txt)
         descs = []
@@ -890,26 +809,15 @@ def _encoder_wgrads(model, pk, gs, M):
                                        batch=nl, batch_strides=(M * n, M * k, _uniform_stride(gws), _uniform_stride(gbs)), sq_slots=slots, tile=4))
         ops.gemm_group(descs, gs.out)
         return
-    fan = rt.fan_streams if (rt.overlap & 8 and all_batched) else []
-    if fan:
-        fork = torch.cuda.Event()
-        fork.record()
-    for i, (g, x, n, k, gws, gbs, kind) in enumerate(kinds):
+    for g, x, n, k, gws, gbs, kind in kinds:
         sw, sb = _uniform_stride(gws), _uniform_stride(gbs)
         if sw is not None and sb is not None and n % 8 == 0 and k % 8 == 0:
             slots = bank.fold_take(ops.sq_slot_count(n, k, nl), "enc:" + kind) if (fresh and rt.dtype == torch.bfloat16) else None
-            branch = contextlib.nullcontext()
-            if fan and i > 0:
-                fan[i - 1].wait_event(fork)
-                branch = _SideStream(fan[i - 1])            # (no K split on a branch: the scratch belongs to the issuing stream)
-            with branch:
-                ops.gemm(g, x, n, k, M, out=gws[0], a_mode=KROW, lda=n, b_mode=KROW, ldb=k, ldc=k, accumulate=not fresh, a_rowsum=gbs[0],
-                         batch=nl, batch_strides=(M * n, M * k, sw, sb), sq_slots=slots)
+            ops.gemm(g, x, n, k, M, out=gws[0], a_mode=KROW, lda=n, b_mode=KROW, ldb=k, ldc=k, accumulate=not fresh, a_rowsum=gbs[0],
+                     batch=nl, batch_strides=(M * n, M * k, sw, sb), sq_slots=slots)
         else:
             for li in range(nl):
                 _linear_wgrad(rt, g[li], x[li], None, None, M, n, k, grad_w=gws[li], grad_b=gbs[li])
-    for st in fan:
-        torch.cuda.current_stream().wait_stream(st)
 
 
 def _ln_offsets(model, dev):
@@ -984,9 +892,8 @@ def encoder_backward(model: ClipBertBaseModel, pk, d_seq, d_pooled):
         d_o_pre, d_o_drop = ln_bwd(2 * li + 1, dx, o_pre, ou.LayerNorm, mean2, rstd2, _seed(_SITE_OUT, li, pk.fwd_i), keep)
         g = d_o_drop if d_o_drop is not None else d_o_pre
         dhp = gs.hp[li]
-        # (which form the forward saved travels in the pack: a backward never multiplies by the wrong one whatever the flag says by now)
-        ops.gemm(g, bank.compute(ou.dense.weight), M, ff, d, out=dhp, b_mode=KROW, gelu_grad_pre=hsave,      # dgrad x GELU'
-                 act=ops.ACT_SAVED_GRAD if pk.gelu_saved_grad else ACT_NONE)
+        ops.gemm(g, bank.compute(ou.dense.weight), M, ff, d, out=dhp, b_mode=KROW, gelu_grad_pre=hsave,      # dgrad x the stored GELU'
+                 act=ops.ACT_SAVED_GRAD)
         da = torch.empty(M, d, dtype=dt, device=dev)
         ops.gemm(dhp, bank.compute(it.dense.weight), M, d, ff, out=da, b_mode=KROW, residual=d_o_pre)
         keep = dict(dx2=gs.att[li]) if pk.p_h > 0 else dict(dx=gs.att[li])
@@ -1001,14 +908,7 @@ def encoder_backward(model: ClipBertBaseModel, pk, d_seq, d_pooled):
         ops.gemm(dqkv, wqkv, M, d, 3 * d, out=dx, b_mode=KROW, residual=d_a_pre)
     if ln_part is not None:
         ops.ln_partials_reduce(ln_part, bank.grad, ln_off[0], ln_off[1])
-    if rt.overlap & 1 and rt.side_stream is not None and rt.after_encoder_backward is None:
-        # the four batched weight-gradient launches on the second branch: they run beside the embedding backwards and the ResNet
-        # backward and are joined where that ends (cnn_backward_steps) or, without a ResNet backward, in _EncoderFn.backward
-        with rt.side(gs.out, gs.hp, gs.att, gs.qkv, stk.x, stk.ctx, stk.a, stk.hact):
-            _encoder_wgrads(model, pk, gs, M)
-    else:
-        _encoder_wgrads(model, pk, gs, M)
-        rt.join()
+    _encoder_wgrads(model, pk, gs, M)
     # ---- embeddings -----------------------------------------------------------------------------------
     if pk.p_h > 0:
         dx = ops.dropout(dx, pk.p_h, _seed(_SITE_EMB, 0, pk.fwd_i), rt.seed_dev)
@@ -1047,8 +947,6 @@ class _EncoderFn(torch.autograd.Function):
         dgrid = encoder_backward(ctx.model, ctx.pack, d_seq, d_pooled)
         ctx.pack = None
         rt = ctx.model.rt
-        if rt.pending_cnn_nodes == 0:
-            rt.join()                                   # (no ResNet backward follows: the side branch ends here)
         rt.pending_encoder_nodes = max(0, rt.pending_encoder_nodes - 1)
         hook = rt.after_encoder_backward
         # a clip LOOP (train_n_clips forwards before one backward) runs several encoder backwards per step: the
@@ -1464,9 +1362,13 @@ class ClipBert(nn.Module):
 
     # ---- MI355X runtime --------------------------------------------------------------------------------
     def prepare(self, dtype=torch.bfloat16, device=None, transformer_lr_mul_prefix="", cnn_lr_mul_prefix="grid_encoder",
-                overlap_wgrad=False):
+                overlap_wgrad=0):
         """Move parameters into the flat HBM buffers and build compute copies.  Call after loading
-        weights / changing requires_grad (freeze_cnn_backbone) and before the first forward."""
+        weights / changing requires_grad (freeze_cnn_backbone) and before the first forward.  ``overlap_wgrad`` must be 0: the
+        weight gradients on concurrent streams were measured slower and removed."""
+        if overlap_wgrad:
+            raise ValueError(f"prepare(overlap_wgrad={overlap_wgrad!r}): weight gradients on side streams were measured slower "
+                             "(profiles/r06a_overlap_ab.txt) and are no longer available; pass 0")
         device = torch.device(device) if device is not None else next(self.parameters()).device
         for buf_owner in self.modules():
             if isinstance(buf_owner, FrozenBatchNorm2d):
@@ -1475,20 +1377,12 @@ class ClipBert(nn.Module):
         rt.dtype = dtype
         # re-preparing (freeze_cnn_backbone on a prepared model) must rebuild the SAME parameter-group layout
         rt.prepare_args = dict(dtype=dtype, device=device, transformer_lr_mul_prefix=transformer_lr_mul_prefix,
-                               cnn_lr_mul_prefix=cnn_lr_mul_prefix, overlap_wgrad=overlap_wgrad)
+                               cnn_lr_mul_prefix=cnn_lr_mul_prefix)
         rt.bank = ParamBank(self, device, dtype, transformer_lr_mul_prefix, cnn_lr_mul_prefix)
         rt.seed_dev = torch.zeros(1, dtype=torch.int64, device=device)
         rt.anchor = torch.zeros(1, dtype=torch.float32, device=device, requires_grad=True)
         if dtype == torch.bfloat16 and (device.type == "cuda" or ops._ALLOW_HOST_POINTERS):
             ops.splitk_workspace(device)            # scratch of cb_gemm's K-split: allocated here, before any hipGraph capture
-        if device.type == "cuda" and overlap_wgrad:
-            # overlap_wgrad: True = every convolution's weight gradient on a second stream (round 1); an int = Runtime.overlap bits
-            rt.overlap = 4 if overlap_wgrad is True else int(overlap_wgrad)
-            rt.side_stream = torch.cuda.Stream(device=device)
-            if rt.overlap & 3 and dtype == torch.bfloat16:
-                rt.side_ws = ops.new_splitk_workspace(device)
-            if rt.overlap & 8:
-                rt.fan_streams = [torch.cuda.Stream(device=device) for _ in range(3)]
         for m in self.modules():
             if hasattr(m, "rt"):
                 m.rt = rt

@@ -112,7 +112,7 @@ def gemm_desc(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, *, out: 
         d.batch = batch
         d.batch_stride_a, d.batch_stride_b, d.batch_stride_c, d.batch_stride_rowsum = batch_strides
     if splitk_ws is None and d.dtype == CB_BF16 and not _SPLITK_OFF:
-        splitk_ws = _SPLITK_SIDE if _SPLITK_SIDE is not None else splitk_workspace(a.device)
+        splitk_ws = splitk_workspace(a.device)
     if splitk_ws is not None:
         d.splitk_ws, d.splitk_ws_bytes = _ptr(splitk_ws), splitk_ws.numel() * splitk_ws.element_size()
     if sq_slots is not None:                  # fp32 slots for the tiles' shares of sum(C^2) (cb_gemm_desc.sq_slots)
@@ -170,15 +170,15 @@ for _item in filter(None, os.environ.get("CB_LAUNCH_OVERRIDE", "").split(";")):
     _k, _, _c = _item.partition("=")
     _LAUNCH_OVERRIDE[tuple(int(x) for x in _k.split(","))] = parse_launch_config(_c)
 _SPLITK_WS = {}
-_SPLITK_OFF = False                    # set while launches go to a SIDE stream (Runtime.side): the buffer belongs to the main stream's launches
-_SPLITK_SIDE = None                    # set while launches go to a side stream that OWNS a scratch of its own (Runtime.side with side_ws)
+_SPLITK_OFF = False                    # True: descriptors get no K-split scratch (split launches add through fp32 atomics; tests of that path)
 SPLITK_WS_BYTES = 128 << 20
 
 
 def splitk_workspace(device) -> torch.Tensor:
     """One fp32 scratch buffer per device for the K-split partial products of cb_gemm's 8-wave tiles.  Launches that follow one
     another on a stream (or on streams ordered by events, as a hipGraph capture after an eager warm-up) share it; launches on a
-    concurrent side stream must not (ops._SPLITK_OFF).  Allocated on first use / by ClipBert.prepare(), never inside a capture."""
+    concurrent stream need a scratch of their own (new_splitk_workspace).  Allocated on first use / by ClipBert.prepare(), never inside a
+    capture."""
     dev = torch.device(device)
     key = str(dev)
     ws = _SPLITK_WS.get(key)
@@ -545,7 +545,7 @@ def sq_slot_count(M: int, N: int, batch: int = 1) -> int:
 
 
 def sq_sum_fold(g, segments, slots, out, ws):
-    """out += sum of g[lo:hi]^2 over ``segments`` (<= 4 (lo, hi) element ranges) + sum(slots): the squared gradient norm of a step whose
+    """out = sum of g[lo:hi]^2 over ``segments`` (<= 4 (lo, hi) element ranges) + sum(slots): the squared gradient norm of a step whose
     weight-gradient launches left their shares in ``slots`` (cb_sq_sum_fold; fixed order of addition)"""
     segs = [(int(lo), int(hi)) for lo, hi in segments if hi > lo]
     assert len(segs) <= 4

@@ -92,8 +92,7 @@ class FusedAdamW:
         self.fold_norm = bool(fold_norm) and max_grad_norm > 0 and bank.compute_dtype == torch.bfloat16
         if self.fold_norm:
             bank.enable_norm_fold()
-        self._sq_own = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._sq = self._sq_own
+        self._sq = torch.zeros(1, dtype=torch.float32, device=dev)           # the squared gradient norm of the last step (grad_norm())
         self._sq_ws = torch.zeros(1024, dtype=torch.float32, device=dev)     # partials of the order-independent norm reduction
         self._last_scale = 1.0
 
@@ -150,21 +149,15 @@ class FusedAdamW:
         reduced gradients this rank holds after the reduce-scatter; only they are updated, ``norm_reduce`` (``sync.norm_all_reduce``)
         sums the squared-norm partials over the ranks, and ``sync.gather_updated()`` afterwards distributes the new weights."""
         bank = self.bank
-        if getattr(bank, "lazy_fresh", False) and not prev:
-            raise RuntimeError("FusedAdamW: zero_grad(lazy=True) was not followed by an encoder backward -- the encoder weight "
-                               "gradients were never written")
-        bank.finish_fresh()                          # first-writer ranges nobody wrote (a partial backward) are zeroed before anything reads them
+        bank.finish(0, bank.n_train, lazy_unwritten_ok=prev)     # (first-writer ranges nobody wrote -- a partial backward -- are zeroed)
         sq = None
         if self.max_grad_norm > 0:
             fold = bank.fold_result() if (self.fold_norm and not reuse_norm and grad16 is None and pieces is None) else None
             if fold is not None:
                 # the weight-gradient launches left their shares of the squared norm in slots (cb_gemm_desc.sq_slots): what remains is the
-                # ranges they do not cover + the slots, added in a fixed order -- no second pass over ~5/6 of the gradient bytes.  The
-                # accumulator was zeroed with the slots by zero_grad(lazy=True).
-                self._sq = bank.sq_buf[:1]
+                # ranges they do not cover + the slots, added in a fixed order and STORED -- no second pass over ~5/6 of the gradient bytes
                 ops.sq_sum_fold(bank.grad, fold[0], fold[1], self._sq, self._sq_ws)
             elif not reuse_norm:
-                self._sq = self._sq_own
                 ops.zero_(self._sq)
                 src = bank.grad if grad16 is None else grad16
                 if pieces is None:
@@ -177,7 +170,7 @@ class FusedAdamW:
             sq = self._sq
         hp_dev = self._hp_dev_prev if prev else self._hp_dev
         if pieces is not None:
-            bank.owner_only_dirty = True          # masters / moments outside the owned pieces are stale until GradSync.gather_state()
+            bank.set_owner_only_dirty(True)       # masters / moments outside the owned pieces are stale until GradSync.gather_state()
         for g, pg in enumerate(self.param_groups):
             a, b = pg["range"]
             if b <= a or (groups is not None and g not in groups):

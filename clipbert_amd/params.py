@@ -102,6 +102,17 @@ class ParamBank:
         self.f_w16 = torch.zeros(max(foff, 1), dtype=torch.bfloat16, device=dev) if compute_dtype == torch.bfloat16 else None
         for _n, p in frozen:
             self._rebind(p, self.f_master, self.f_offset[id(p)], grad=False)
+        # ---- gradient epoch: one per zero_grad; what its launches have written so far ----
+        self.grad_epoch = 0                 # GradSync.wait() tells a repeated wait() (nothing to do) from a step whose exchange was never issued
+        self.lazy_span = None               # (lo, hi) of the encoder weight gradients (set_lazy_span)
+        self.lazy_fresh = False             # the lazy span holds stale values: its next producer stores (take_fresh)
+        self.fresh_span = None              # (lo, hi) of the ResNet's convolution weight gradients (set_fresh_params)
+        self.fresh_ids: Dict[int, tuple] = {}     # id(parameter) -> its (lo, hi) inside fresh_span
+        self.fresh_left = set()             # ids of fresh-range parameters no launch has written this epoch (take_fresh_param / finish)
+        self.sq_buf: Optional[torch.Tensor] = None      # squared-norm share slots (enable_norm_fold)
+        self.fold = None                    # this epoch's use of the slots: dict(valid, next, covers) -- None: no shares
+        self.norm_fold_blocked = False      # block_norm_fold(): the norm is taken of exchanged gradients, not of the shares
+        self.owner_only_dirty = False       # set_owner_only_dirty(): masters / moments are sharded over the ranks
         self.sync_compute()
 
     def _view(self, flat: torch.Tensor, off: int, like: torch.Tensor) -> torch.Tensor:
@@ -187,84 +198,89 @@ class ParamBank:
         ``zero_grad(lazy=True)`` skips that range and the first producer after it overwrites (first-writer stores: no memset
         and no fp32 read-modify-write for ~57 % of the gradient bytes)."""
         self.lazy_span, self.lazy_fresh = None, False
-        ps = [p for p in params if id(p) in self.offset]
-        if not ps or len(ps) != len(list(params)):
-            return
-        spans = sorted((self.offset[id(p)], self.offset[id(p)] + (p.numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN) for p in ps)
-        for (a0, b0), (a1, _b1) in zip(spans, spans[1:]):
-            if b0 != a1:
-                return                                  # another parameter sits in between
-        self.lazy_span = (spans[0][0], spans[-1][1])
+        spans = self._tiling(params)
+        if spans is not None and len(spans) == len(params):
+            self.lazy_span = (spans[0][0], spans[-1][1])
 
     def set_fresh_params(self, params):
         """``params``: parameters whose weight gradient is produced by ONE launch per backward that can store instead of accumulate
         (the ResNet's convolution weights: cb_gemm accumulate = 2, first writer).  If they tile one contiguous range of the flat gradient
         buffer, ``zero_grad(lazy=True)`` skips it too; ``take_fresh_param`` tells each producer whether it is the first writer of this
-        step, and ``finish_fresh`` zeroes what no producer wrote (a partial backward) before the gradients are read."""
+        step, and ``finish`` zeroes what no producer wrote (a partial backward) before the gradients are read."""
         self.fresh_span, self.fresh_ids, self.fresh_left = None, {}, set()
-        ps = [p for p in params if id(p) in self.offset]
-        if not ps:
-            return
-        spans = sorted((self.offset[id(p)], self.offset[id(p)] + (p.numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN, id(p)) for p in ps)
-        for (_a0, b0, _i0), (a1, _b1, _i1) in zip(spans, spans[1:]):
-            if b0 != a1:
-                return                                  # another parameter sits in between
-        if any(p.numel() % self.ALIGN for p in ps):
+        spans = self._tiling(params)
+        if spans is None or any(p.numel() % self.ALIGN for p in params if id(p) in self.offset):
             return                                      # (padding inside the range would never be written)
         self.fresh_span = (spans[0][0], spans[-1][1])
         self.fresh_ids = {i: (a, b) for a, b, i in spans}
 
+    def _tiling(self, params):
+        """sorted (lo, hi, id) of the trainable ``params`` if they tile one contiguous range of the flat gradient buffer, else None"""
+        spans = sorted((self.offset[id(p)], self.offset[id(p)] + (p.numel() + self.ALIGN - 1) // self.ALIGN * self.ALIGN, id(p))
+                       for p in params if id(p) in self.offset)
+        if not spans or any(b0 != a1 for (_a0, b0, _i0), (a1, _b1, _i1) in zip(spans, spans[1:])):
+            return None                                 # (another parameter sits in between)
+        return spans
+
     def take_fresh_param(self, p: nn.Parameter) -> bool:
         """True exactly once per gradient epoch for a parameter of the fresh range: its gradient holds garbage and must be STORED now"""
-        left = getattr(self, "fresh_left", None)
-        if left and id(p) in left:
-            left.discard(id(p))
+        if id(p) in self.fresh_left:
+            self.fresh_left.discard(id(p))
             return True
         return False
 
-    def finish_fresh(self):
-        """zero the gradients of fresh-range parameters no producer wrote since zero_grad(lazy=True) (called before anything reads them)"""
-        left = getattr(self, "fresh_left", None)
+    def finish(self, lo: int, hi: int, lazy_unwritten_ok: bool = False) -> int:
+        """Make gradients [lo, hi) readable; every reader of ``grad`` calls this first (FusedAdamW.launch, GradSync).  Zeroes the
+        first-writer parameters overlapping the range that no launch wrote this epoch (a partial backward) and returns how many; raises
+        if the range overlaps the lazy span and no encoder backward wrote it (``lazy_unwritten_ok``: an update of the previous step)."""
+        span = self.lazy_span
+        if self.lazy_fresh and not lazy_unwritten_ok and span is not None and span[0] < hi and lo < span[1]:
+            raise RuntimeError("ParamBank: zero_grad(lazy=True) was not followed by an encoder backward -- the encoder weight "
+                               "gradients were never written")
+        left = sorted((self.fresh_ids[i], i) for i in self.fresh_left if self.fresh_ids[i][0] < hi and lo < self.fresh_ids[i][1])
+        for (a, b), i in left:
+            ops.zero_(self.grad[a:b])
+            self.fresh_left.discard(i)
         if left:
-            for i in sorted(left):
-                a, b = self.fresh_ids[i]
-                ops.zero_(self.grad[a:b])
-            left.clear()
             self.fold_invalidate()
+        return len(left)
 
     # ---- squared-norm shares (cb_gemm_desc.sq_slots): the weight-gradient launches of a step leave sum(dW^2) per output tile in slots ----
     SQ_SLOTS = 1 << 16
 
     def enable_norm_fold(self):
-        """allocate the accumulator + slots (zeroed by zero_grad(lazy=True) from then on); idempotent"""
-        if getattr(self, "sq_buf", None) is None:
-            self.sq_buf = torch.zeros(1 + self.SQ_SLOTS, dtype=torch.float32, device=self.device)
-            self.fold = None
+        """allocate the slots (zeroed by zero_grad(lazy=True) from then on); idempotent"""
+        if self.sq_buf is None:
+            self.sq_buf = torch.zeros(self.SQ_SLOTS, dtype=torch.float32, device=self.device)
         return self.sq_buf
+
+    def block_norm_fold(self):
+        """the norm of every step is taken of exchanged gradients (GradSync): no launch leaves shares, fold_result() is None"""
+        self.norm_fold_blocked = True
 
     def fold_take(self, slots: int, covers: str):
         """``slots`` slots for one weight-gradient launch of the running step (None: no share wanted / possible); ``covers``: what the
         launch writes completely -- one of the four encoder kinds ("enc:<kind>") or one fresh-range parameter ("cnn")"""
-        f = getattr(self, "fold", None)
-        if f is None or not f["valid"] or getattr(self, "norm_fold_blocked", False):
+        f = self.fold
+        if f is None or not f["valid"] or self.norm_fold_blocked:
             return None
         if f["next"] + slots > self.SQ_SLOTS:
             f["valid"] = False
             return None
-        view = self.sq_buf[1 + f["next"]:1 + f["next"] + slots]
+        view = self.sq_buf[f["next"]:f["next"] + slots]
         f["next"] += slots
         f["covers"].append(covers)
         return view
 
     def fold_invalidate(self):
-        if getattr(self, "fold", None) is not None:
+        if self.fold is not None:
             self.fold["valid"] = False
 
     def fold_result(self):
         """(segments, slots) for ops.sq_sum_fold if the shares of this step are usable: every encoder kind stored once, every fresh-range
         parameter stored once with a share -- else None (the caller runs the full pass)"""
-        f = getattr(self, "fold", None)
-        if f is None or not f["valid"] or getattr(self, "lazy_fresh", False) or getattr(self, "fresh_left", None) or getattr(self, "norm_fold_blocked", False):
+        f = self.fold
+        if f is None or not f["valid"] or self.lazy_fresh or self.fresh_left or self.norm_fold_blocked:
             return None
         covered = []
         enc = [c for c in f["covers"] if c.startswith("enc:")]
@@ -273,7 +289,7 @@ class ParamBank:
         elif enc:
             return None                                  # (a partial set of shares inside the lazy span cannot be subtracted)
         ncnn = sum(1 for c in f["covers"] if c == "cnn")
-        if getattr(self, "fresh_span", None) is not None and ncnn == len(self.fresh_ids):
+        if self.fresh_span is not None and ncnn == len(self.fresh_ids):
             covered.append(self.fresh_span)
         elif ncnn:
             return None
@@ -286,22 +302,33 @@ class ParamBank:
             lo = b
         if lo < self.n_train:
             segs.append((lo, self.n_train))
-        return segs, self.sq_buf[1:1 + f["next"]]
+        return segs, self.sq_buf[:f["next"]]
+
+    def set_owner_only_dirty(self, dirty: bool):
+        """owner-only updates (GradSync(shard=True)) left the masters / moments sharded over the ranks (True) or gathered them (False)"""
+        self.owner_only_dirty = dirty
 
     def assert_whole(self, what: str):
         """Owner-only updates (GradSync(shard=True)) leave every rank with ITS pieces of the fp32 masters and AdamW moments: anything
         that reads the whole state (state_dict(), a checkpoint) needs GradSync.gather_state() on all ranks first."""
-        if getattr(self, "owner_only_dirty", False):
+        if self.owner_only_dirty:
             raise RuntimeError(f"{what}: the parameters / optimizer moments are sharded over the ranks (owner-only update) -- "
                                "call GradSync.gather_state(optimizer) on every rank first")
+
+    def begin_epoch(self, lazy: bool = False):
+        """Start a gradient epoch (GradSync.wait() counts them) whose zeroing the caller does itself (zero_grad_range); ``lazy``: the
+        lazy span was left as it is -- its producer stores instead of accumulating."""
+        self.grad_epoch += 1
+        self.lazy_fresh = lazy and self.lazy_span is not None
+        self.fresh_left = set()
+        self.fold = None
 
     def zero_grad(self, lazy: bool = False):
         """lazy=True: the caller guarantees that a full backward follows before the gradients are read; the lazy span (see
         set_lazy_span) is then left as it is and marked fresh -- its producer stores instead of accumulating."""
-        self.grad_epoch = getattr(self, "grad_epoch", 0) + 1       # one per gradient group: GradSync.wait() tells a repeated wait()
-        span = getattr(self, "lazy_span", None)                   # (nothing to do) from a step whose exchange was never issued
-        if lazy and span is not None:
-            skip = sorted([span] + ([self.fresh_span] if getattr(self, "fresh_span", None) is not None else []))
+        self.begin_epoch(lazy)
+        if lazy and self.lazy_span is not None:
+            skip = sorted([self.lazy_span] + ([self.fresh_span] if self.fresh_span is not None else []))
             lo = 0
             fills = []                                         # (the gaps around the first-writer ranges + the norm slots: ONE launch, cb_zero_ranges)
             for a, b in skip:
@@ -310,24 +337,20 @@ class ParamBank:
                 lo = max(lo, b)
             if lo < self.grad.numel():
                 fills.append(self.grad[lo:])
-            self.lazy_fresh = True
-            self.fresh_left = set(getattr(self, "fresh_ids", {}))
-            if getattr(self, "sq_buf", None) is not None:      # the norm accumulator and this step's share slots start at zero
+            self.fresh_left = set(self.fresh_ids)
+            if self.sq_buf is not None:                        # this step's share slots start at zero
                 fills.append(self.sq_buf)
                 self.fold = dict(valid=True, next=0, covers=[])
             ops.zero_many(fills)
         else:
             ops.zero_(self.grad)
-            self.lazy_fresh = False
-            self.fresh_left = set()
-            self.fold = None
 
     def zero_grad_range(self, lo: int, hi: int, lazy: bool = False):
         """zero_grad restricted to [lo, hi) of the flat gradient buffer (a step whose halves are zeroed at different points, see
         FusedAdamW.launch(groups=...)); ``lazy`` as in zero_grad: the lazy span is skipped.  Does not start a new gradient epoch."""
         self.fresh_left = set()                                   # (the half-step plans zero every range they own: no first writers)
         self.fold = None
-        span = getattr(self, "lazy_span", None) if lazy else None
+        span = self.lazy_span if lazy else None
         if span is None or span[1] <= lo or span[0] >= hi:
             if hi > lo:
                 ops.zero_(self.grad[lo:hi])
@@ -340,7 +363,7 @@ class ParamBank:
 
     def take_fresh(self) -> bool:
         """True once after zero_grad(lazy=True): the lazy span holds stale values and must be overwritten (or zeroed) now"""
-        fresh = getattr(self, "lazy_fresh", False)
+        fresh = self.lazy_fresh
         self.lazy_fresh = False
         return fresh
 

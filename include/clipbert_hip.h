@@ -389,7 +389,7 @@ int cb_sq_sum(const float* g, int64_t n, float* out_accum, void* stream);
  * gradients derive the bit-identical clip coefficient (torch.nn.utils.clip_grad_norm_ in run_video_retrieval.py:477-482 is
  * deterministic per rank too).  ws: caller-owned scratch of ws_floats floats. */
 int cb_sq_sum_det(const float* g, int64_t n, float* out_accum, float* ws, int32_t ws_floats, void* stream);
-/* The norm of a step whose weight-gradient launches already left their shares in slots (cb_gemm_desc.sq_slots): out_accum += the squares
+/* The norm of a step whose weight-gradient launches already left their shares in slots (cb_gemm_desc.sq_slots): out_accum = the squares
  * of the nseg (<= 4) ranges g[seg_lo_hi[2 i], seg_lo_hi[2 i + 1]) that no such launch covers (seg_lo_hi: HOST array of element
  * offsets) + the sum of slots[0, nslots), everything added in a fixed order (same determinism contract as cb_sq_sum_det).  Two launches. */
 int cb_sq_sum_fold(const float* g, const int64_t* seg_lo_hi, int32_t nseg, const float* slots, int64_t nslots, float* out_accum, float* ws,

@@ -306,7 +306,7 @@ def test_first_writer_weight_gradients_and_norm_shares(hw, grouped):
     assert torch.equal(slots, slots2)
     assert float(slots[-7:].abs().sum()) == 0.0                          # nobody writes past its reservation
     extra = hw(rnd(1003, seed=77))                                       # a range no launch covered (unaligned length)
-    total = torch.zeros(1, device=hw.dev)
+    total = torch.full((1,), float("nan"), device=hw.dev)              # garbage: cb_sq_sum_fold STORES the total (out =), it does not add to it
     scratch = torch.empty(1024, device=hw.dev)
     ops.sq_sum_fold(extra, [(3, 1003), (0, 3)], slots, total, scratch)
     want = sum(float((o.double() ** 2).sum()) for o in outs) + float((extra.double() ** 2).sum())

@@ -322,3 +322,13 @@ def test_regression_head_matches_oracle(hw, train_bn):
         assert float((bn.running_mean.cpu() - sd["transformer.regressor.2.running_mean"]).abs().max()) > 0
     else:
         torch.testing.assert_close(bn.running_var.cpu(), sd["transformer.regressor.2.running_var"], rtol=0, atol=0)
+
+
+def test_prepare_rejects_overlap_wgrad(hw):
+    """the side-stream weight-gradient variants were measured slower and removed: prepare() accepts overlap_wgrad=0 / False only"""
+    cfg, _sd, model = build("retrieval", dict(num_labels=2, loss_type="ce", margin=0.1), torch.bfloat16, hw.dev)
+    for off in (0, False):
+        model.prepare(dtype=torch.bfloat16, device=hw.dev, overlap_wgrad=off)
+    for bits in (1, 2, 4, 8, True):
+        with pytest.raises(ValueError, match="r06a_overlap_ab"):
+            model.prepare(dtype=torch.bfloat16, device=hw.dev, overlap_wgrad=bits)
