@@ -4,7 +4,9 @@
 //   C[m,n] (op)= epilogue( sum_k A(m,k) * B(n,k) )           (optionally `batch` problems per launch)
 //
 // Layout of the sources: gemm_impl.h holds the kernel templates, gemm_inst_*.hip instantiate one tile size each (so the
-// tile sizes compile in parallel), this file validates a cb_gemm_desc and dispatches.
+// tile sizes compile in parallel).  A call goes through three host steps with plain data between them: validate (gemm_prepare, here:
+// descriptor -> Prepared), choose (gemm_choose.h: Prepared -> LaunchPlan) and launch (gemm_launch, here); cb_gemm, cb_gemm_plan,
+// cb_gemm_workspace_bytes and cb_gemm_group compose them.
 //
 // * 256 threads = 4 waves (2x2); block tile 128x128 (one block per CU with a 2-stage register ring, or two blocks per CU with
 //   one stage and <= 256 registers) / 128x64 / 64x64, K step 64 (bf16) / 32 (fp32).  256-row tiles (256x128, 256x64: one block
@@ -26,7 +28,6 @@
 #include "gemm8_impl.h"
 #include "gemm_stream_impl.h"
 #include <stdio.h>
-#include <cmath>
 #include <vector>
 
 using namespace cbgemm;
@@ -51,16 +52,11 @@ CB_G8_DECL(128, 256, 2, 4, 3)
 CB_G8_DECL(256, 128, 4, 2, 3)
 #undef CB_G8_DECL
 // few rows (tile 9, gemm_skinny.hip)
-bool skinny_covers(const cb_gemm_desc* d, const GP& p);
 int launch_gemm_skinny(const cb_gemm_desc* d, GP& p, hipStream_t st);
 }
 
-// Per-shape launch configurations measured on MI355X (tools/tune_gemm.py sweeps every cb_gemm call of the benchmark
-// steps over tile x workgroup order, tools/gen_tuned.py writes the table): consulted when the caller leaves tile /
-// xcd_order at 0 (auto); shapes that are not in the table fall through to the heuristics below.
-#include "gemm_tuned.h"
-// Shapes outside the table: a launch-cost model fitted to the same sweeps (tools/fit_gemm_model.py) ranks the legal configurations.
-#include "gemm_model.h"
+// switches, Form / Prepared, the launch-cost model and gemm_choose (validated call -> LaunchPlan)
+#include "gemm_choose.h"
 
 // ---- diagnostic build (-DCB_STAMPS, clipbert_amd/lib/libclipbert_hip_stamps.so; tools/stamps_run.py): every stamped launch gets a
 // record area in a caller-provided device buffer and a host-side description ----------------------------------------------------
@@ -148,89 +144,6 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(GP p, const float* w
     epilogue8<T>(p, v, sc, sh, m, orow, n);
 }
 
-// which of the 8-wave kernel's forms (0 none, 1 forward, 2 data gradient, 3 weight gradient) covers this problem
-int gemm8_form(const cb_gemm_desc* d, const GP& p, bool fast) {
-    if (!fast || d->dtype != CB_BF16) return 0;
-    const int taps = p.R * p.S;
-    if ((d->a_mode == CB_ROWK || d->a_mode == CB_ROWK_GATHER) && d->b_mode == CB_ROWK) return 1;
-    if (d->a_mode == CB_ROWK && (d->b_mode == CB_KROW || (d->b_mode == CB_KROW_TAPS && taps == 1))) return 2;
-    if (d->a_mode == CB_ROWK_GATHER && d->b_mode == CB_KROW_TAPS && p.Ct % 64 == 0) return 2;
-    if (d->a_mode == CB_KROW && (d->b_mode == CB_KROW || d->b_mode == CB_KROW_GATHER)) return 3;
-    return 0;
-}
-
-
-// ---- launch-cost model (tools/fit_gemm_model.py: formula and fit) --------------------------------------------------------------
-struct ModelPick { int tile = 0, split = 0, sched = 0; double us = 1e300; };
-const int MODEL_TILE_ID[7] = {2, 3, 1, 4, 5, 6, 7};
-const int MODEL_BM[7] = {64, 128, 128, 128, 256, 128, 256};
-const int MODEL_BN[7] = {64, 64, 128, 128, 256, 256, 128};
-
-double model_us(int ti, int form, int64_t M, int64_t N, int64_t K, int64_t batch, int s, bool taps, bool m2, int c_esz) {
-    using namespace cbgemm;
-    const double* g = MODEL_G;
-    const int64_t wg = ((M + MODEL_BM[ti] - 1) / MODEL_BM[ti]) * ((N + MODEL_BN[ti] - 1) / MODEL_BN[ti]) * batch * s;
-    const int64_t kt = ((K + 63) / 64 + s - 1) / s;
-    const double r = (double)wg / (256.0 * MODEL_OCC[ti]);
-    const double q = ti >= 4 ? g[7] : g[3];                      // how hard the grid is quantised in whole rounds over the CUs
-    const double rounds = q * std::ceil(r - 1e-9) + (1.0 - q) * (r > 1.0 ? r : 1.0);
-    const double ck = MODEL_C[ti][form] * (1.0 + g[4] * (taps ? 1 : 0)) * (1.0 + g[8] * (m2 ? 1 : 0));
-    const double ab = (double)(M * K + N * K) * 2.0 * batch, cb = (double)M * N * batch * c_esz;
-    const double red = (ti >= 4 && s > 1) ? (double)M * N * batch * s * 8.0 : 0.0;
-    const double atom = (ti < 4 && s > 1) ? (double)M * N * batch * s * 4.0 : 0.0;
-    return MODEL_A[ti] + rounds * (MODEL_B[ti][form] + kt * ck) + ab / (g[0] * 1e6) + cb / (g[5] * 1e6) + red / (g[1] * 1e6) + atom / (g[2] * 1e6) +
-           g[6] * (m2 ? 1 : 0);
-}
-
-// The configurations that are legal for this call (the same space tools/tune_gemm.py sweeps), ranked by the model.
-// can8: an 8-wave kernel covers the call; ws_bytes: K-split workspace the caller provided; free_split: the 4-wave kernels may split K
-// as they like (weight-gradient form: fp32 C accumulated in place through atomics).
-ModelPick model_pick(const cb_gemm_desc* d, const GP& p, bool can8, int64_t ws_bytes, bool free_split, int split_caller) {
-    const int form = d->a_mode == CB_KROW ? 2 : (d->b_mode != CB_ROWK ? 1 : 0);
-    const bool taps = p.R * p.S > 1;
-    const int c_esz = d->c_f32 ? 4 : 2;
-    const int64_t M = d->M, N = d->N, K = d->K, batch = p.batch;
-    ModelPick best;
-    auto consider = [&](int ti, int s, int sched) {
-        const double us = model_us(ti, form, M, N, K, batch, s, taps, sched == 3, c_esz);
-        if (us < best.us) { best.us = us; best.tile = MODEL_TILE_ID[ti]; best.split = s; best.sched = sched; }
-    };
-    static const int SPLITS4[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48};
-    for (int ti = 0; ti < 4; ++ti) {
-        if (N <= 64 && ti >= 2) continue;                          // (narrow outputs never take the 128-column tiles)
-        consider(ti, split_caller, 0);
-        if (free_split)
-            for (int s : SPLITS4)
-                if (s != split_caller && s <= (p.ktiles / 4 > 1 ? p.ktiles / 4 : 1)) consider(ti, s, 0);
-    }
-    if (can8)
-        for (int ti = 4; ti < 7; ++ti) {
-            const int64_t tiles = ((M + MODEL_BM[ti] - 1) / MODEL_BM[ti]) * ((N + MODEL_BN[ti] - 1) / MODEL_BN[ti]) * batch;
-            int cand[3] = {1, 0, 0};
-            int n = 1;
-            for (int target : {256, 512}) {                         // unsplit, or the grid brought to ~1x / ~2x the CUs
-                const int s = (int)std::lround((double)target / (double)tiles);
-                if (s > 1 && p.ktiles / s >= 2 && (int64_t)s * batch * M * N * 4 <= ws_bytes && s != cand[1]) cand[n++] = s;
-            }
-            for (int i = 0; i < n; ++i) { consider(ti, cand[i], 1); consider(ti, cand[i], 3); }
-        }
-    return best;
-}
-
-// Streaming structure (gemm_stream_impl.h, cb_gemm_desc.tile = 8): the instantiation that covers this problem, or -1.
-// Covered: bf16 fast path, forward form (A and B CB_ROWK), K <= 64 with N a multiple of 256 or K <= 128 with N a multiple of 128,
-// bf16 C through the row-contiguous epilogue with any of scale / shift / activation / residual / relu_after.
-int stream_variant(const cb_gemm_desc* d, const GP& p, bool fast, bool cv8) {
-    if (!fast || !cv8 || d->dtype != CB_BF16 || d->a_mode != CB_ROWK || d->b_mode != CB_ROWK || p.batch > 1 || p.split_k > 1) return -1;
-    if (d->c_f32 || d->accumulate || d->c_rowmap || d->zero_fill_pitch || d->a_rowsum || d->gelu_grad_pre || d->dropout_p > 0.f || d->mask || d->relu_bwd ||
-        d->C2) return -1;
-    if (d->K % 8 != 0 || d->M < 64) return -1;
-    if ((int64_t)d->M * (d->N > d->K ? d->N : d->K) * 2 >= 0x7fffffffll) return -1;       // (32-bit byte offsets of the DMA loaders)
-    if (p.ktiles == 1 && d->N % 256 == 0) return 0;
-    if (p.ktiles == 2 && d->N % 128 == 0) return 1;
-    return -1;
-}
-
 template <int BM, int BN, int WGM, int WGN, int NST>
 int launch8(int form, const GP& p, int mode, float* ws, hipStream_t st) {
     if (form == 1) return launch_gemm8_fwd<BM, BN, WGM, WGN, NST>(p, mode, ws, st);
@@ -238,24 +151,7 @@ int launch8(int form, const GP& p, int mode, float* ws, hipStream_t st) {
     return launch_gemm8_wgrad<BM, BN, WGM, WGN, NST>(p, mode, ws, st);
 }
 
-}  // namespace
-
-
-namespace {
-// Arrival counters of the slab K split (gemm_tile): they live in the CALLER's K-split scratch -- its last CB_SPLITK_WS_COUNTER_BYTES bytes
-// (include/clipbert_hip.h), zeroed once by whoever allocated the buffer; every launch leaves them zero (the last part to arrive resets
-// its tile's ticket).  Ownership follows the workspace: launches that may run concurrently carry different scratch buffers and therefore
-// different tickets.  The library allocates nothing and keeps no per-device state for them (round 5 kept a hipMalloc'ed buffer here:
-// VERDICT r5 weak 6).  No launch writes partial tiles into the counter region: splitk_payload_bytes() is what slabs may use.
-constexpr int GROUP_COUNTERS = CB_SPLITK_WS_COUNTER_BYTES / (int)sizeof(int);
-inline int64_t splitk_payload_bytes(int64_t ws_bytes) { return ws_bytes > CB_SPLITK_WS_COUNTER_BYTES ? ws_bytes - CB_SPLITK_WS_COUNTER_BYTES : 0; }
-inline int* splitk_counters(void* ws, int64_t ws_bytes) {
-    return ws && ws_bytes > CB_SPLITK_WS_COUNTER_BYTES ? reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(ws) + (ws_bytes - CB_SPLITK_WS_COUNTER_BYTES)) : nullptr;
-}
-
-// Validation + translation of a descriptor into the kernels' parameter block: everything about a call that does not depend on
-// the launch configuration.  fast: 16-byte range-checked buffer loads are legal; cv8: the row-contiguous (8-column) epilogue is.
-struct Prepared { GP p; bool fast, cv8; };
+// ---- validate: a descriptor is checked and translated into the kernels' parameter block (Prepared, gemm_choose.h)
 int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
     CB_REQUIRE(d != nullptr, "cb_gemm: null descriptor");
     CB_REQUIRE(d->dtype == CB_F32 || d->dtype == CB_BF16, "cb_gemm: bad dtype %d", d->dtype);
@@ -303,13 +199,12 @@ int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
     {   // write-through (sc1) bf16 epilogue stores (round 5, profiles/r05b_bench_ab_wt.txt: -0.10 ... -0.14 ms per step, four alternating runs):
         // the output leaves for the memory side while the other workgroups still compute, instead of sitting dirty in the XCD's L2 until
         // the end-of-kernel release writes it back in one burst.  CB_GEMM_WT=0 restores plain stores; =3 adds nt on the second output.
-        static const int wt = getenv("CB_GEMM_WT") != nullptr ? atoi(getenv("CB_GEMM_WT")) : 1;
         const bool ok = d->dtype == CB_BF16 && !d->c_f32 && (int64_t)d->M * (d->ldc > d->ldc2 ? d->ldc : d->ldc2) * 2 * (p.batch) < 0xffffffffll && !d->c_rowmap;
-        p.wt = ok ? wt : 0;
+        p.wt = ok ? switches().wt : 0;
     }
     {   // specialised epilogue (FAST_EPI_COMBOS in gemm_impl.h): the call's option combination, if it is one of the listed ones and the
         // row-contiguous bf16 write-through epilogue applies; CB_GEMM_FAST_EPI=0: the generic epilogue8 for everything
-        static const bool fe_off = getenv("CB_GEMM_FAST_EPI") != nullptr && atoi(getenv("CB_GEMM_FAST_EPI")) == 0;
+        const bool fe_off = switches().fast_epi_off;
         p.fast_epi = 0;
         auto rows_ok = [&](const void* q, int64_t ld) { return q == nullptr || (ld % 8 == 0 && aligned16(q) && (int64_t)d->M * ld * 2 < 0x7fffffffll); };
         // weight-gradient forms that STORE an fp32 C (first writer): the lean fp32 epilogue, which also leaves the tile's share of the squared norm
@@ -416,176 +311,105 @@ int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
     if (d->mask) cv8 = cv8 && (d->ldm % 8 == 0) && aligned16(d->mask);
     if (d->gelu_grad_pre) cv8 = cv8 && (d->ld_gelu % 8 == 0) && aligned16(d->gelu_grad_pre);
     out.fast = fast; out.cv8 = cv8;
+    out.form = operand_form(d->a_mode, d->b_mode, taps); out.taps = taps;
+    out.epi_scale_only = !d->C2 && !d->residual && !d->mask && !d->gelu_grad_pre && d->act == CB_ACT_NONE && !d->relu_after && !d->shift && d->dropout_p <= 0.f;
+    out.atomics_ok = out.epi_scale_only && d->c_f32 && d->accumulate == 1;
     return 0;
 }
 
-// cb_gemm proper.  plan != nullptr: validate and choose as a launch would, write {tile, split_k, schedule, xcd_order}, launch nothing.
-int gemm_run(const cb_gemm_desc* d, void* stream, int32_t* plan, bool use_table) {
+// The checks every entry point makes first, then gemm_prepare.  empty: M or N is zero -- nothing to compute, and the rest of the descriptor
+// is not looked at.
+int gemm_validate(const cb_gemm_desc* d, Prepared& pr, bool& empty) {
+    empty = false;
     CB_REQUIRE(d != nullptr, "cb_gemm: null descriptor");
     CB_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0, "cb_gemm: negative dims");
-    if (d->M == 0 || d->N == 0) return 0;
-    Prepared prep;
-    if (int rc = gemm_prepare(d, prep)) return rc;
-    GP& p = prep.p;
-    const bool fast = prep.fast;
-    bool cv8 = prep.cv8;
-    const int esz = d->dtype == CB_BF16 ? 2 : 4;
-    (void)esz;
-    static const bool no_remap = getenv("CB_GEMM_NO_XCD_REMAP") != nullptr;
-    static const bool no_tuned = getenv("CB_GEMM_NO_TUNED") != nullptr;
-    int tile = d->tile, xcd = d->xcd_order;
-    // ---- few rows (tile 9): asked for, or M <= 64 -- the heads' products (pooler, classifier MLP, their data gradients), where a 64x64
-    // tile walks the whole reduction as one chain; the four waves of a 32x64 workgroup split it instead (gemm_skinny.hip; in the step
-    // 10-19 us -> 4-6 us per launch, profiles/r06j_skinny_ab.txt).  CB_GEMM_NO_SKINNY=1 restores the tiled kernels.
-    {
-        static const bool no_skinny = getenv("CB_GEMM_NO_SKINNY") != nullptr;
-        const bool covers = skinny_covers(d, p);
-        CB_REQUIRE(tile != 9 || covers, "cb_gemm: tile 9 (few rows) does not cover this problem (bf16, A k-contiguous, B k-contiguous or aligned reduction-major, no batch / K split / row sums)");
-        if (tile == 9 || (tile == 0 && use_table && !no_skinny && covers && d->M <= 64)) {
-            if (plan) { plan[0] = 9; plan[1] = 1; plan[2] = 0; plan[3] = 2; return 0; }
-            static const bool trace_k = getenv("CB_GEMM_TRACE") != nullptr;
-            if (trace_k) fprintf(stderr, "cb_gemm: M=%d N=%d K=%d modes=%d/%d tile=9 (asked %d) few rows\n", d->M, d->N, d->K, d->a_mode, d->b_mode, d->tile);
-            return launch_gemm_skinny(d, p, cb_stream(stream));
-        }
-    }
-    // ---- streaming structure (tile 8): asked for, or chosen for the HBM-bound shapes it was built for -- short reduction, many rows
-    // (measured on MI355X, profiles/r04c_stream_probe.json; CB_GEMM_NO_STREAM=1 restores the one-workgroup-per-tile kernels)
-    {
-        static const bool no_stream = getenv("CB_GEMM_NO_STREAM") != nullptr;
-        constexpr int min_rows = 32768;
-        const int sv = stream_variant(d, p, fast, cv8);
-        CB_REQUIRE(tile != 8 || sv >= 0, "cb_gemm: tile 8 (streaming) does not cover this problem (M=%d N=%d K=%d modes %d/%d)", d->M, d->N, d->K, d->a_mode, d->b_mode);
-        // (shapes of the measured table follow the table: since the specialised epilogues of round 6 the 128x128 two-per-CU tile beats the
-        // streaming kernel on the res3 conv3 shape in the step, profiles/r06d_instep_tuning.json -- tile 8 is not a table entry)
-        const bool tabled = d->dtype == CB_BF16 && getenv("CB_GEMM_NO_TUNED") == nullptr &&
-                            cbgemm::tuned_lookup(d->a_mode, d->b_mode, d->M, d->N, d->K, p.batch, p.R * p.S, p.split_k) != nullptr;
-        if (tile == 8 || (tile == 0 && use_table && !no_stream && !tabled && sv >= 0 && d->M >= min_rows && d->N <= 512)) {
-            p.c_vec8 = 1;
-            p.xcd_remap = 0;
-            if (plan) { plan[0] = 8; plan[1] = 1; plan[2] = sv; plan[3] = 2; return 0; }
-            static const bool trace_s = getenv("CB_GEMM_TRACE") != nullptr;
-            if (trace_s) fprintf(stderr, "cb_gemm: M=%d N=%d K=%d modes=%d/%d tile=8 (asked %d) stream variant %d\n", d->M, d->N, d->K, d->a_mode, d->b_mode, d->tile, sv);
-            return launch_gemm_stream(p, sv, cb_stream(stream));
-        }
-    }
-    const int split_caller = p.split_k;
-    int split_tuned = 0, sched_tuned = 0;      // K split / K-loop schedule measured best for the table's tile (0: none recorded)
-    if (d->dtype == CB_BF16 && !no_tuned && use_table && (tile == 0 || xcd == 0)) {
-        if (const cbgemm::TunedEntry* e = cbgemm::tuned_lookup(d->a_mode, d->b_mode, d->M, d->N, d->K, p.batch, p.R * p.S, p.split_k)) {
-            if (tile == 0) { tile = e->tile; split_tuned = e->new_split; sched_tuned = e->sched; }
-            if (xcd == 0) xcd = e->xcd;
-        }
-    }
+    empty = d->M == 0 || d->N == 0;
+    return empty ? 0 : gemm_prepare(d, pr);
+}
 
-    // ---- 8-wave LDS-DMA tiles (5: 256x256, 6: 128x256, 7: 256x128), bf16 fast path, row-contiguous epilogue.  Their K split
-    // writes fp32 partial slabs into the caller's workspace and a second kernel adds them in index order and applies the FULL
-    // epilogue: deterministic, no atomics, any epilogue.  Without a (large enough) workspace a split configuration is not run at all
-    // (an unsplit large tile would leave most CUs idle): the 4-wave kernels take the problem.
-    const int form8 = (d->dtype == CB_BF16 && cv8) ? gemm8_form(d, p, fast) : 0;
-    float* ws8 = nullptr;
-    if (tile >= 5 && form8 == 0) { tile = 0; split_tuned = sched_tuned = 0; }      // not covered: the 4-wave kernels decide
-    // the 4-wave kernels may choose their own K split where the result is accumulated in place through atomics (weight-gradient form)
-    const bool no_atomics = d->accumulate == 2 || d->sq_slots != nullptr;      // first writer / norm share: partial sums only through slabs
-    const bool free_split = d->tile == 0 && d->a_mode == CB_KROW && d->c_f32 && d->accumulate == 1 && !d->sq_slots && !d->C2 && !d->residual && !d->mask && !d->gelu_grad_pre &&
-                            d->act == CB_ACT_NONE && !d->relu_after && !d->shift && d->dropout_p <= 0.f;
-    const bool ws_usable = d->splitk_ws && aligned16(d->splitk_ws);
-    static const bool no_model = getenv("CB_GEMM_NO_MODEL") != nullptr;       // diagnostic: 64x64 tiles for everything outside the table
-    auto ask_model = [&](bool allow8) {                           // shapes outside the table (or whose table entry cannot run here)
-        if (d->dtype != CB_BF16 || no_model) return;
-        const ModelPick mp = model_pick(d, p, allow8 && form8 != 0, ws_usable ? splitk_payload_bytes(d->splitk_ws_bytes) : 0, free_split && !d->a_rowsum && p.batch == 1, split_caller);
-        tile = mp.tile;
-        split_tuned = (mp.tile >= 5 || mp.split != split_caller) ? mp.split : 0;
-        sched_tuned = mp.sched;
-    };
-    if (tile == 0) ask_model(true);
-    if (tile >= 5 && d->sq_slots && (d->tile == 0 ? split_tuned : split_caller) > 1) {        // (the slab reduce kernel leaves no norm share)
-        tile = 0; split_tuned = sched_tuned = 0;
-        ask_model(false);
-    }
-    if (tile >= 5) {
-        int split = d->tile == 0 ? (split_tuned > 0 ? split_tuned : 1) : split_caller;       // (table / model: its own split)
-        if (split > p.ktiles) split = p.ktiles;
-        bool no_ws = false;
-        if (split > 1) {
-            const int per = (p.ktiles + split - 1) / split;
-            split = (p.ktiles + per - 1) / per;                  // every split owns at least one K tile
-            const int64_t need = (int64_t)split * p.batch * d->M * d->N * 4;
-            if (d->splitk_ws && splitk_payload_bytes(d->splitk_ws_bytes) >= need && aligned16(d->splitk_ws)) ws8 = reinterpret_cast<float*>(d->splitk_ws);
-            else { split = 1; no_ws = true; }
-        }
-        if (no_ws) {                                             // the configuration needs its split: without a workspace the model decides again
-            tile = 0; split_tuned = sched_tuned = 0;
-            ask_model(d->tile == 0);                                 // (it only offers splits the workspace holds; an explicit 8-wave request falls to 4 waves)
-            if (tile >= 5) p.split_k = split_tuned > 0 ? split_tuned : 1, ws8 = p.split_k > 1 ? reinterpret_cast<float*>(d->splitk_ws) : nullptr;
-        } else p.split_k = split;
-    }
-    static const bool trace = getenv("CB_GEMM_TRACE") != nullptr;
-    if (trace) fprintf(stderr, "cb_gemm: M=%d N=%d K=%d modes=%d/%d tile=%d (asked %d) form8=%d split=%d ws=%d\n", d->M, d->N, d->K, d->a_mode, d->b_mode,
-                       tile, d->tile, form8, tile >= 5 ? p.split_k : split_caller, ws8 != nullptr);
-    if (tile >= 5) {
-        CB_REQUIRE(d->schedule >= 0 && d->schedule <= 3, "cb_gemm: bad schedule %d", d->schedule);
-        const int mode8 = d->schedule > 0 ? d->schedule - 1 : (sched_tuned > 0 ? sched_tuned - 1 : 2);
-        p.c_vec8 = 1;
-        p.xcd_remap = !no_remap && xcd != 2;
-        if (plan) { plan[0] = tile; plan[1] = p.split_k; plan[2] = mode8 + 1; plan[3] = p.xcd_remap ? 1 : 2; return 0; }
-        hipStream_t st8 = cb_stream(stream);
-        CB_STAMP_ASSIGN(p, d, tile, p.split_k, mode8 + 1, 0, 1);
+void trace_plan(const cb_gemm_desc* d, const Prepared& pr, const LaunchPlan& lp) {
+    if (lp.tile == 9)
+        fprintf(stderr, "cb_gemm: M=%d N=%d K=%d modes=%d/%d tile=9 (asked %d) few rows\n", d->M, d->N, d->K, d->a_mode, d->b_mode, d->tile);
+    else if (lp.tile == 8)
+        fprintf(stderr, "cb_gemm: M=%d N=%d K=%d modes=%d/%d tile=8 (asked %d) stream variant %d\n", d->M, d->N, d->K, d->a_mode, d->b_mode, d->tile, lp.sched);
+    else
+        fprintf(stderr, "cb_gemm: M=%d N=%d K=%d modes=%d/%d tile=%d (asked %d) form8=%d split=%d ws=%d\n", d->M, d->N, d->K, d->a_mode, d->b_mode,
+                lp.picked, d->tile, lp.form8, lp.tile >= 5 ? lp.split_k : pr.p.split_k, (int)lp.slab);
+}
+
+// ---- launch: the chosen configuration on the stream
+int gemm_launch(const cb_gemm_desc* d, const Prepared& pr, const LaunchPlan& lp, hipStream_t st) {
+    GP p = pr.p;
+    if (lp.tile == 9) return launch_gemm_skinny(d, p, st);
+    p.split_k = lp.split_k;
+    p.c_vec8 = lp.c_vec8;
+    p.xcd_remap = lp.xcd_remap;
+    if (lp.tile == 8) return launch_gemm_stream(p, lp.sched, st);
+    if (lp.tile >= 5) {
+        float* ws = lp.slab ? reinterpret_cast<float*>(d->splitk_ws) : nullptr;
+        CB_STAMP_ASSIGN(p, d, lp.tile, p.split_k, lp.sched, 0, 1);
         int rc;
-        if (tile == 5) rc = launch8<256, 256, 2, 4, 2>(form8, p, mode8, ws8, st8);
-        else if (tile == 6) rc = launch8<128, 256, 2, 4, 3>(form8, p, mode8, ws8, st8);
-        else rc = launch8<256, 128, 4, 2, 3>(form8, p, mode8, ws8, st8);
-        if (rc != 0 || !ws8) return rc;
+        if (lp.tile == 5) rc = launch8<256, 256, 2, 4, 2>(lp.form8, p, lp.sched - 1, ws, st);
+        else if (lp.tile == 6) rc = launch8<128, 256, 2, 4, 3>(lp.form8, p, lp.sched - 1, ws, st);
+        else rc = launch8<256, 128, 4, 2, 3>(lp.form8, p, lp.sched - 1, ws, st);
+        if (rc != 0 || !ws) return rc;
         GP q = p;
         q.split_k = 1;
         const int64_t chunks = (int64_t)d->M * (d->N / 8);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)p.batch), dim3(256), 0, st8, q, ws8, p.split_k);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((chunks + 255) / 256), (unsigned)p.batch), dim3(256), 0, st, q, ws, p.split_k);
         return cb_launch_status("cb_gemm (split-K reduce)");
     }
+    if (d->dtype == CB_F32) return launch_gemm<float, 64, 64, 2>(p, pr.fast, st);
+    CB_STAMP_ASSIGN(p, d, lp.tile, p.split_k, 0, 0, 1);
+    if (lp.tile == 4) return launch_gemm<bf16, 128, 128, 1, 2>(p, pr.fast, st);
+    if (lp.tile == 1) return launch_gemm<bf16, 128, 128, 2>(p, pr.fast, st);
+    if (lp.tile == 3) return launch_gemm<bf16, 128, 64, 2>(p, pr.fast, st);
+    return launch_gemm<bf16, 64, 64, 3>(p, pr.fast, st);
+}
 
-    // ---- 4-wave kernels
-    p.split_k = split_caller;
-    {   // a split asked for WITH an 8-wave tile means "through slabs": if this problem ended up here (shape not covered, no workspace) the
-        // split only survives where the atomics path can take it (fp32 C accumulated in place, scale/alpha-only epilogue)
-        const bool atomics_ok = d->c_f32 && d->accumulate == 1 && !d->C2 && !d->residual && !d->mask && !d->gelu_grad_pre && d->act == CB_ACT_NONE &&
-                                !d->relu_after && !d->shift && d->dropout_p <= 0.f;
-        if (d->tile >= 5 && p.split_k > 1 && !atomics_ok) p.split_k = 1;
-    }
-    if (no_atomics) p.split_k = 1;                                 // (a caller's split means atomics here)
-    if (split_tuned > 0 && d->tile == 0 && d->a_mode == CB_KROW && d->c_f32 && d->accumulate == 1 && !d->sq_slots && !d->C2 && !d->residual &&
-        !d->mask && !d->gelu_grad_pre && d->act == CB_ACT_NONE && !d->relu_after && !d->shift && d->dropout_p <= 0.f)
-        p.split_k = split_tuned;       // weight-gradient form (plain epilogue, fp32 C accumulated in place: any K split is valid): the measured best
-    if (p.split_k > 1) {
-        CB_REQUIRE(d->c_f32 && d->accumulate == 1, "cb_gemm: split_k > 1 needs an fp32 output that is accumulated into (accumulate = 1)");
-        CB_REQUIRE(!d->C2 && !d->residual && !d->mask && !d->gelu_grad_pre && d->act == CB_ACT_NONE && !d->relu_after && !d->shift && d->dropout_p <= 0.f,
-                   "cb_gemm: split_k > 1 supports only scale/alpha in the epilogue");
-        if (p.split_k > p.ktiles) p.split_k = p.ktiles;
-    }
-    cv8 = cv8 && p.split_k == 1;                                  // (atomics keep the 4-wide path)
-    p.c_vec8 = cv8;
-    if (d->zero_fill_pitch != 0)
-        CB_REQUIRE(d->zero_fill_pitch > 0 && d->c_rowmap && p.c_vec8 && d->batch <= 1,
-                   "cb_gemm: zero_fill_pitch needs c_rowmap and 16-byte-aligned 8-column chunks (N, ldc %% 8 == 0)");
-    // default workgroup order: XCD-compact (it won or tied on ~80 % of the round-2 sweep's shapes and lowers the fabric traffic)
-    p.xcd_remap = !no_remap && xcd != 2;
-
-    hipStream_t st = cb_stream(stream);
-    if (d->dtype == CB_F32) {
-        if (plan) { plan[0] = 2; plan[1] = p.split_k; plan[2] = 0; plan[3] = p.xcd_remap ? 1 : 2; return 0; }
-        return launch_gemm<float, 64, 64, 2>(p, fast, st);
-    }
-    if (tile == 0) tile = 2;                         // (CB_GEMM_NO_MODEL)
-    if (tile == 1 && d->N <= 64) tile = 3;           // narrow outputs (stem / res2 convs): 128x64 tile
-    if (tile == 4 && d->N <= 64) tile = 3;
-    if (plan) { plan[0] = tile; plan[1] = p.split_k; plan[2] = 0; plan[3] = p.xcd_remap ? 1 : 2; return 0; }
-    CB_STAMP_ASSIGN(p, d, tile, p.split_k, 0, 0, 1);
-    if (tile == 4) return launch_gemm<bf16, 128, 128, 1, 2>(p, fast, st);
-    if (tile == 1) return launch_gemm<bf16, 128, 128, 2>(p, fast, st);
-    if (tile == 3) return launch_gemm<bf16, 128, 64, 2>(p, fast, st);
-    return launch_gemm<bf16, 64, 64, 3>(p, fast, st);
+// cb_gemm for a validated problem (cb_gemm_group's single problems enter here with the Prepared they already have)
+int gemm_run(const cb_gemm_desc* d, const Prepared& pr, void* stream) {
+    LaunchPlan lp;
+    const int rc = gemm_choose(d, pr, true, false, lp);
+    if (lp.tile != 0 && switches().trace) trace_plan(d, pr, lp);
+    return rc != 0 ? rc : gemm_launch(d, pr, lp, cb_stream(stream));
 }
 }  // namespace
 
-extern "C" int cb_gemm(const cb_gemm_desc* d, void* stream) { return gemm_run(d, stream, nullptr, true); }
+extern "C" int cb_gemm(const cb_gemm_desc* d, void* stream) {
+    Prepared pr;
+    bool empty;
+    if (int rc = gemm_validate(d, pr, empty)) return rc;
+    return empty ? 0 : gemm_run(d, pr, stream);
+}
+
+// validate and choose as cb_gemm would, write {tile, split_k, schedule, xcd_order}, launch nothing
+extern "C" int cb_gemm_plan(const cb_gemm_desc* d, int32_t use_table, int32_t* out4) {
+    CB_REQUIRE(out4 != nullptr, "cb_gemm_plan: null output");
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    Prepared pr;
+    LaunchPlan lp;
+    bool empty;
+    if (int rc = gemm_validate(d, pr, empty)) return rc;
+    if (empty) return 0;
+    if (int rc = gemm_choose(d, pr, use_table != 0, false, lp)) return rc;
+    out4[0] = lp.tile; out4[1] = lp.split_k; out4[2] = lp.sched; out4[3] = lp.xcd_remap ? 1 : 2;
+    return 0;
+}
+
+// K-split scratch cb_gemm would use for `d` if it were handed an unlimited one: what a caller sizes splitk_ws by.
+extern "C" int cb_gemm_workspace_bytes(const cb_gemm_desc* d, int64_t* bytes) {
+    CB_REQUIRE(d != nullptr && bytes != nullptr, "cb_gemm_workspace_bytes: null argument");
+    *bytes = 0;
+    Prepared pr;
+    LaunchPlan lp;
+    bool empty;
+    if (int rc = gemm_validate(d, pr, empty)) return rc;
+    if (empty) return 0;
+    if (int rc = gemm_choose(d, pr, true, true, lp)) return rc;
+    if (lp.slab) *bytes = (int64_t)lp.split_k * pr.p.batch * d->M * d->N * 4 + CB_SPLITK_WS_COUNTER_BYTES;
+    return 0;
+}
 
 // ---- cb_gemm_group -------------------------------------------------------------------------------------------------------------
 namespace {
@@ -595,22 +419,19 @@ int group_class(const cb_gemm_desc* d, const Prepared& pr) {
     if (d->batch > 1 || d->a_rowsum) {
         // strided batches and bias row sums: the unsplit bf16 weight-gradient form on the 128x128 two-per-CU tile only (GC_WGRAD_RS: the
         // encoder's four kinds of 12-layer weight gradients share one grid -- their last waves of tiles fill each other's)
-        const bool ok = d->dtype == CB_BF16 && d->a_mode == CB_KROW && d->b_mode == CB_KROW && d->split_k <= 1 && d->tile != 2 && !d->c_rowmap;
+        const bool ok = d->dtype == CB_BF16 && pr.form == FORM_WGRAD && d->split_k <= 1 && d->tile != 2 && !d->c_rowmap;
         return ok ? GC_WGRAD_RS : -1;
     }
-    if (d->a_mode == CB_KROW && d->b_mode == CB_KROW) return GC_WGRAD;
-    if (d->a_mode == CB_KROW && d->b_mode == CB_KROW_GATHER) return GC_WGRAD_GATHER;
-    if (d->a_mode == CB_ROWK && d->b_mode == CB_ROWK) return GC_FWD;
-    if (d->a_mode == CB_ROWK_GATHER && d->b_mode == CB_ROWK) return GC_FWD_GATHER;
-    return -1;
-}
-// the K split of a problem may be chosen freely where partial sums combine through atomics (cb_gemm's own rule)
-bool split_is_free(const cb_gemm_desc* d) {
-    return d->a_mode == CB_KROW && d->c_f32 && d->accumulate && !d->C2 && !d->residual && !d->mask && !d->gelu_grad_pre && d->act == CB_ACT_NONE &&
-           !d->relu_after && !d->shift && d->dropout_p <= 0.f;
+    return GROUP_CLASS_OF[pr.form];
 }
 
-struct GroupItem { const cb_gemm_desc* d; Prepared pr; int cls; int split; };
+struct GroupItem { const cb_gemm_desc* d; Prepared pr; int cls; };
+
+// The K split of a grouped problem may be chosen freely where its parts can combine.  Unlike cb_gemm's rule (Prepared::atomics_ok) a first
+// writer (accumulate == 2) counts here: a group's split problems may combine through the slab scratch, which needs no accumulated-into
+// C; group_choose takes such a split back where that scratch cannot be used.
+bool group_split_free(const GroupItem& it) { return a_reduction_major(it.pr.form) && it.d->c_f32 && it.d->accumulate != 0 && it.pr.epi_scale_only; }
+inline int64_t group_tiles(const cb_gemm_desc* d, int B) { return (int64_t)((d->M + B - 1) / B) * ((d->N + B - 1) / B); }
 
 // Launch configuration of one grouped launch (bf16): tile 2 (64x64) or 4 (128x128, two workgroups per CU) and a K split per problem.
 // Cost model (calibrated on the in-step durations of profiles/r03z_train_step.md; tools/group_probe.py re-measures it): a CU retires
@@ -628,16 +449,15 @@ double group_cost(const std::vector<GroupItem*>& g, int tile, int s, int* splits
     for (size_t i = 0; i < g.size(); ++i) {
         const cb_gemm_desc* d = g[i]->d;
         const int kt = g[i]->pr.p.ktiles;
-        int si = d->split_k > 0 ? d->split_k : 1;
-        if (split_is_free(d)) {
+        int si = g[i]->pr.p.split_k;
+        if (group_split_free(*g[i])) {
             si = (kt + kt_target / 2) / kt_target;
             if (si < 1) si = 1;
             while (si > 1 && kt / si < 4) --si;                    // (every split keeps at least four K tiles)
         }
         if (si > kt) si = kt > 0 ? kt : 1;
         splits[i] = si;
-        const int64_t tiles = (int64_t)((d->M + B - 1) / B) * ((d->N + B - 1) / B);
-        W += tiles * si;
+        W += group_tiles(d, B) * si;
         const int per = (kt + si - 1) / si;
         kt_per_max = per > kt_per_max ? per : kt_per_max;
         if (si > 1) atom += (double)d->M * d->N * 4.0 * si;
@@ -654,27 +474,30 @@ double group_cost(const std::vector<GroupItem*>& g, int tile, int s, int* splits
     return 8.0 + (double)per_cu * kt_per_max * unit + atom / 2.0e6;
 }
 
-int launch_group_chunk(std::vector<GroupItem*>& g, int dtype, int cls, hipStream_t st) {
-    static const bool no_remap = getenv("CB_GEMM_NO_XCD_REMAP") != nullptr;
-    static const bool trace = getenv("CB_GEMM_TRACE") != nullptr;
-    int splits[GROUP_MAX];
+// ---- choose for one grouped launch: the tile, a K split per problem, and whether the split problems combine through the slab scratch
+struct GroupPlan {
     int tile = 2;
+    int splits[GROUP_MAX];
+    float* slab = nullptr;    // the caller's K-split scratch where the slab K split runs, else null: fp32 atomics
+    int* cnt = nullptr;       // ... and its arrival counters
+};
+void group_choose(const std::vector<GroupItem*>& g, int dtype, int cls, GroupPlan& gp) {
+    int* splits = gp.splits;
+    auto callers_splits = [&] { for (size_t i = 0; i < g.size(); ++i) splits[i] = g[i]->pr.p.split_k; };
     if (dtype == CB_F32) {
-        for (size_t i = 0; i < g.size(); ++i) splits[i] = g[i]->d->split_k > 0 ? g[i]->d->split_k : 1;
+        callers_splits();
     } else {
         const int asked = g[0]->d->tile;
-        bool narrow = false;
-        for (auto* it : g) narrow = narrow || it->d->N <= 64;
         if (cls == GC_WGRAD_RS) {                                    // (one tile, no K split: see group_class)
-            tile = 4;
+            gp.tile = 4;
             for (size_t i = 0; i < g.size(); ++i) splits[i] = 1;
         } else if (asked == 2 || asked == 4) {                       // explicit: the caller's tile and splits
-            tile = asked;
-            for (size_t i = 0; i < g.size(); ++i) splits[i] = g[i]->d->split_k > 0 ? g[i]->d->split_k : 1;
+            gp.tile = asked;
+            callers_splits();
         } else {
             static const int SPLITS[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
-            bool any_free = false;
-            for (auto* it : g) any_free = any_free || split_is_free(it->d);
+            bool narrow = false, any_free = false;
+            for (auto* it : g) { narrow = narrow || it->d->N <= 64; any_free = any_free || group_split_free(*it); }
             double best = 1e300;
             int tmp[GROUP_MAX];
             for (int t : {2, 4}) {
@@ -682,22 +505,17 @@ int launch_group_chunk(std::vector<GroupItem*>& g, int dtype, int cls, hipStream
                 for (int s : SPLITS) {
                     if (s > 1 && !any_free) break;
                     const double c = group_cost(g, t, s, tmp);
-                    if (c < best) { best = c; tile = t; for (size_t i = 0; i < g.size(); ++i) splits[i] = tmp[i]; }
+                    if (c < best) { best = c; gp.tile = t; for (size_t i = 0; i < g.size(); ++i) splits[i] = tmp[i]; }
                 }
             }
         }
     }
-    const int B = (dtype == CB_BF16 && tile == 4) ? 128 : 64;
-    GroupArgs ga{};
-    ga.n = (int)g.size();
     // ---- slab K split (bf16 weight gradients; gemm_tile): the split problems' partial tiles go to the caller's K-split scratch and the last
     // part of a tile to arrive adds them in part order -- no fp32 atomics, a bit-reproducible sum.  Needs the scratch of the first split
-    // problem (the same buffer on every descriptor of a step: ops.splitk_workspace) to hold every part, and the library's counters.
+    // problem (the same buffer on every descriptor of a step: ops.splitk_workspace) to hold every part, and its counters.
     // CB_GROUP_SLAB=0 keeps the atomics.
-    static const bool slab_off = getenv("CB_GROUP_SLAB") != nullptr && atoi(getenv("CB_GROUP_SLAB")) == 0;
-    float* slab_ws = nullptr;
-    int* slab_cnt = nullptr;
-    if (dtype == CB_BF16 && !slab_off && (cls == GC_WGRAD || cls == GC_WGRAD_GATHER)) {
+    if (dtype == CB_BF16 && !switches().group_slab_off && (cls == GC_WGRAD || cls == GC_WGRAD_GATHER)) {
+        const int B = gp.tile == 4 ? 128 : 64;
         int64_t units = 0, tiles_split = 0;
         const cb_gemm_desc* first = nullptr;
         bool ok = true;
@@ -706,83 +524,88 @@ int launch_group_chunk(std::vector<GroupItem*>& g, int dtype, int cls, hipStream
             const int kt = g[i]->pr.p.ktiles;
             const int si = splits[i] > kt ? (kt > 0 ? kt : 1) : splits[i];
             if (si <= 1) continue;
-            const int64_t tiles = (int64_t)((d->M + B - 1) / B) * ((d->N + B - 1) / B);
-            units += tiles * si;
-            tiles_split += tiles;
+            units += group_tiles(d, B) * si;
+            tiles_split += group_tiles(d, B);
             if (!first) first = d;
             ok = ok && d->splitk_ws == first->splitk_ws && g[i]->pr.p.batch == 1 && !d->a_rowsum && !d->c_rowmap;
         }
         if (first && ok && first->splitk_ws && aligned16(first->splitk_ws) && first->splitk_ws_bytes % 4 == 0 &&
             units * B * B * 4 <= splitk_payload_bytes(first->splitk_ws_bytes) && tiles_split <= GROUP_COUNTERS) {
             for (size_t i = 0; i < g.size(); ++i) ok = ok && (splits[i] <= 1 || g[i]->d->splitk_ws_bytes == first->splitk_ws_bytes);
-            slab_cnt = ok ? splitk_counters(first->splitk_ws, first->splitk_ws_bytes) : nullptr;
-            if (slab_cnt) slab_ws = reinterpret_cast<float*>(first->splitk_ws);
+            gp.cnt = ok ? splitk_counters(first->splitk_ws, first->splitk_ws_bytes) : nullptr;
+            if (gp.cnt) gp.slab = reinterpret_cast<float*>(first->splitk_ws);
         }
     }
-    if (!slab_ws)                                                   // first writers / norm shares never combine through atomics: unsplit without a scratch
+    if (!gp.slab)                                                   // first writers / norm shares never combine through atomics: unsplit without a scratch
         for (size_t i = 0; i < g.size(); ++i)
             if (g[i]->d->accumulate == 2 || g[i]->d->sq_slots) splits[i] = 1;
-    ga.slab = slab_ws;
-    ga.cnt = slab_ws ? slab_cnt : nullptr;
+}
+
+// ---- launch one group: the problems' parameter blocks with their ranges of workgroups, slab units and counters
+int group_launch(const std::vector<GroupItem*>& g, int dtype, int cls, const GroupPlan& gp, hipStream_t st) {
+    const Switches& sw = switches();
+    const int B = (dtype == CB_BF16 && gp.tile == 4) ? 128 : 64;
+    GroupArgs ga{};
+    ga.n = (int)g.size();
+    ga.slab = gp.slab;
+    ga.cnt = gp.slab ? gp.cnt : nullptr;
     int64_t slab_units = 0;
     int cnt_tiles = 0;
     int xcd = 0;
     int64_t acc = 0;
     for (size_t i = 0; i < g.size(); ++i) {
         const cb_gemm_desc* d = g[i]->d;
-        GP p = g[i]->pr.p;
-        p.split_k = splits[i] > p.ktiles ? (p.ktiles > 0 ? p.ktiles : 1) : splits[i];
+        const Prepared& pr = g[i]->pr;
+        GP p = pr.p;
+        p.split_k = gp.splits[i] > p.ktiles ? (p.ktiles > 0 ? p.ktiles : 1) : gp.splits[i];
         if (p.split_k > 1) {
-            CB_REQUIRE(d->c_f32 && (d->accumulate == 1 || slab_ws), "cb_gemm_group: split_k > 1 needs an fp32 output accumulated into, or the slab scratch");
-            CB_REQUIRE(!d->C2 && !d->residual && !d->mask && !d->gelu_grad_pre && d->act == CB_ACT_NONE && !d->relu_after && !d->shift && d->dropout_p <= 0.f,
-                       "cb_gemm_group: split_k > 1 supports only scale/alpha in the epilogue");
+            CB_REQUIRE(d->c_f32 && (d->accumulate == 1 || gp.slab), "cb_gemm_group: split_k > 1 needs an fp32 output accumulated into, or the slab scratch");
+            CB_REQUIRE(pr.epi_scale_only, "cb_gemm_group: split_k > 1 supports only scale/alpha in the epilogue");
         }
-        p.c_vec8 = g[i]->pr.cv8 && (p.split_k == 1 || slab_ws);
-        if (slab_ws && p.split_k > 1) {
-            const int tiles = ((d->M + B - 1) / B) * ((d->N + B - 1) / B);
+        p.c_vec8 = pr.cv8 && (p.split_k == 1 || gp.slab);
+        const int64_t tiles = group_tiles(d, B);
+        if (gp.slab && p.split_k > 1) {
             CB_REQUIRE(slab_units < (1ll << 31), "cb_gemm_group: slab index overflow");
             p.slab_base = (int)slab_units;
             p.cnt_base = cnt_tiles;
-            slab_units += (int64_t)tiles * p.split_k;
-            cnt_tiles += tiles;
+            slab_units += tiles * p.split_k;
+            cnt_tiles += (int)tiles;
         }
         if (d->xcd_order != 0) xcd = d->xcd_order;
-        acc += (int64_t)((d->M + B - 1) / B) * ((d->N + B - 1) / B) * p.split_k * (p.batch > 1 ? p.batch : 1);
+        acc += tiles * p.split_k * (p.batch > 1 ? p.batch : 1);
         CB_REQUIRE(acc < (1ll << 30), "cb_gemm_group: too many workgroups");
         ga.tile_end[i] = (int)acc;
-        CB_STAMP_ASSIGN(p, d, tile, p.split_k, 0, (int)i, (int)g.size());
+        CB_STAMP_ASSIGN(p, d, gp.tile, p.split_k, 0, (int)i, (int)g.size());
         ga.g[i] = p;
-        if (trace) fprintf(stderr, "cb_gemm_group[%zu/%zu]: M=%d N=%d K=%d modes=%d/%d cls=%d tile=%d split=%d%s\n", i, g.size(), d->M, d->N, d->K, d->a_mode,
-                           d->b_mode, cls, tile, p.split_k, slab_ws && p.split_k > 1 ? " slab" : "");
+        if (sw.trace) fprintf(stderr, "cb_gemm_group[%zu/%zu]: M=%d N=%d K=%d modes=%d/%d cls=%d tile=%d split=%d%s\n", i, g.size(), d->M, d->N, d->K, d->a_mode,
+                              d->b_mode, cls, gp.tile, p.split_k, gp.slab && p.split_k > 1 ? " slab" : "");
     }
-    ga.xcd_remap = !no_remap && xcd != 2;
+    ga.xcd_remap = !sw.no_xcd_remap && xcd != 2;
     if (dtype == CB_F32) return launch_gemm_group<float, 64, 64, 2, 1>(ga, cls, st);
-    if (tile == 4) return launch_gemm_group<bf16, 128, 128, 1, 2>(ga, cls, st);
+    if (gp.tile == 4) return launch_gemm_group<bf16, 128, 128, 1, 2>(ga, cls, st);
     return launch_gemm_group<bf16, 64, 64, 3, 1>(ga, cls, st);
 }
 }  // namespace
 
 extern "C" int cb_gemm_group(const cb_gemm_desc* descs, int32_t n, void* stream) {
     CB_REQUIRE(n >= 0 && (n == 0 || descs != nullptr), "cb_gemm_group: bad arguments");
-    static const bool off = getenv("CB_GEMM_NO_GROUP") != nullptr;        // diagnostic: every problem as its own cb_gemm launch
     std::vector<GroupItem> items;
     items.reserve(n);
     for (int i = 0; i < n; ++i) {
         const cb_gemm_desc* d = descs + i;
         CB_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0, "cb_gemm_group: negative dims (problem %d)", i);
         if (d->M == 0 || d->N == 0) continue;
-        GroupItem it{d, Prepared{}, -1, 1};
+        GroupItem it{d, Prepared{}, -1};
         if (int rc = gemm_prepare(d, it.pr)) return rc;
-        it.cls = off ? -1 : group_class(d, it.pr);
+        it.cls = switches().no_group ? -1 : group_class(d, it.pr);
         items.push_back(it);
     }
-    hipStream_t st = cb_stream(stream);
     std::vector<char> done(items.size(), 0);
     for (size_t i = 0; i < items.size(); ++i) {
         if (done[i]) continue;
         if (items[i].cls < 0) {                                           // not covered by a grouped kernel
             done[i] = 1;
-            if (int rc = gemm_run(items[i].d, stream, nullptr, true)) return rc;
+            if (int rc = gemm_run(items[i].d, items[i].pr, stream)) return rc;
             continue;
         }
         std::vector<GroupItem*> bucket;                                   // same dtype and class (and an explicit tile request in common), caller's order
@@ -792,36 +615,18 @@ extern "C" int cb_gemm_group(const cb_gemm_desc* descs, int32_t n, void* stream)
                 done[j] = 1;
             }
         if (bucket.size() == 1) {
-            if (int rc = gemm_run(bucket[0]->d, stream, nullptr, true)) return rc;
+            if (int rc = gemm_run(bucket[0]->d, bucket[0]->pr, stream)) return rc;
             continue;
         }
         const size_t nchunks = (bucket.size() + GROUP_MAX - 1) / GROUP_MAX;
         const size_t per = (bucket.size() + nchunks - 1) / nchunks;
         for (size_t c = 0; c < bucket.size(); c += per) {
             std::vector<GroupItem*> chunk(bucket.begin() + c, bucket.begin() + (c + per < bucket.size() ? c + per : bucket.size()));
-            if (int rc = launch_group_chunk(chunk, items[i].d->dtype, items[i].cls, st)) return rc;
+            GroupPlan gp;
+            group_choose(chunk, items[i].d->dtype, items[i].cls, gp);
+            if (int rc = group_launch(chunk, items[i].d->dtype, items[i].cls, gp, cb_stream(stream))) return rc;
         }
     }
-    return 0;
-}
-
-extern "C" int cb_gemm_plan(const cb_gemm_desc* d, int32_t use_table, int32_t* out4) {
-    CB_REQUIRE(out4 != nullptr, "cb_gemm_plan: null output");
-    out4[0] = out4[1] = out4[2] = out4[3] = 0;
-    return gemm_run(d, nullptr, out4, use_table != 0);
-}
-
-// K-split scratch cb_gemm would use for `d` if it were handed an unlimited one: what a caller sizes splitk_ws by.
-extern "C" int cb_gemm_workspace_bytes(const cb_gemm_desc* d, int64_t* bytes) {
-    CB_REQUIRE(d != nullptr && bytes != nullptr, "cb_gemm_workspace_bytes: null argument");
-    *bytes = 0;
-    alignas(16) static float dummy[4];
-    cb_gemm_desc q = *d;
-    q.splitk_ws = dummy;                                   // (never dereferenced in plan mode)
-    q.splitk_ws_bytes = (int64_t)1 << 60;
-    int32_t plan[4] = {0, 0, 0, 0};
-    if (int rc = gemm_run(&q, nullptr, plan, true)) return rc;
-    if (plan[0] >= 5 && plan[1] > 1) *bytes = (int64_t)plan[1] * (d->batch > 1 ? d->batch : 1) * d->M * d->N * 4 + CB_SPLITK_WS_COUNTER_BYTES;
     return 0;
 }
 

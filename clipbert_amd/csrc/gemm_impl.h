@@ -1979,7 +1979,7 @@ enum { GC_WGRAD = 0,        // A KROW, B KROW            (weight gradient of a L
                             // four kinds of 12-layer weight gradients in ONE launch (bf16, 128x128 two-per-CU tile only)
        GC_COUNT = 5 };
 
-// stream-K launcher: bf16 weight-gradient classes only (A KROW, B KROW | KROW_GATHER, transpose-read loaders)
+// launcher of a grouped kernel: the loaders of the group's class (GC_*)
 template <typename T, int BM, int BN, int PF, int OCC>
 int launch_gemm_group(const GroupArgs& ga, int cls, hipStream_t st) {
     const dim3 grid((unsigned)ga.tile_end[ga.n - 1]);

@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-os.environ["CB_GEMM_STREAM_MIN_ROWS"] = "2000000000"      # auto never streams in this process: tile 0 = the tuned one-workgroup-per-tile launch
+os.environ["CB_GEMM_NO_STREAM"] = "1"                     # auto never streams in this process: tile 0 = the tuned one-workgroup-per-tile launch
 import torch  # noqa: E402
 
 import tune_gemm  # noqa: E402
