@@ -52,6 +52,7 @@ _SIGNATURES = {
     "cb_gemm_workspace_bytes": [vp, vp],
     "cb_build_pixel_table": [vp, i32, i32, i32, i32, i32, i64, i64, i64, vp],
     "cb_stem_pack": [i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "cb_resize_pack_u8": [i32, vp, i64, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp],
     "cb_image_norm": [vp, vp, vp, vp, i64, i64, vp],
     "cb_maxpool_fwd": [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "cb_maxpool2_bwd": [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],

@@ -7,15 +7,166 @@ materialised per batch).  Here
 * frames stay **uint8** all the way into HBM (1 byte per pixel over PCIe and in HBM); the cast, mean / std and the RGB->BGR
   flip happen inside the stem's input pack (``cb_stem_pack(src_u8=1)``) -- ``img_normalize`` is therefore not a tensor op here
   but the (mean, std) pair handed to the model;
+* that holds for the decoder's **native-resolution** frames too: ``RawFrames`` (built by ``collate_raw_frames``) carries a
+  ragged batch -- every video its own height and width -- as one flat uint8 buffer plus a geometry table, and the reference's
+  per-frame ``ImageResize`` (bilinear, longer side -> max_img_size) + ``ImagePad`` (src/datasets/dataset_base.py:270-273,
+  src/datasets/data_utils.py:112-253) run on the GPU inside ``cb_resize_pack_u8``, which writes the stem's packed image
+  directly.  No fp32 frame is ever built on the host;
 * host staging is **pinned and double-buffered**: two pinned slots per tensor key, batch i+1 is copied host->pinned->HBM on a
   side HIP stream while batch i computes; a slot is reused only after the event recorded behind its last H2D copy has
   completed, and the consumer stream waits on the copy's event (not on the whole side stream);
 * ``InfiniteIterator`` as in the reference (:155-175).
 
 Host code + HIP streams / events (through torch): plumbing, no arithmetic."""
-from typing import Dict, Iterable, Iterator, Optional
+from typing import Dict, Iterable, Iterator, Optional, Sequence
 
 import torch
+
+
+# ---- the reference's resize arithmetic (host integers only) ------------------------------------------------------------------
+def resize_size(h: int, w: int, max_size: int):
+    """(new_h, new_w) of the reference's ImageResize (get_resize_size, src/datasets/data_utils.py:167-199): the longer side becomes
+    ``max_size``, the shorter one ``max_size * short / long`` evaluated in Python floats and TRUNCATED (333 x 500 at 768 ->
+    511 x 768, not 512); a square frame counts as portrait.  Pinned to the reference by tests/test_resize_pack.py."""
+    long_side, short_side = max(h, w), min(h, w)
+    other = int(max_size * (short_side / long_side))
+    return (int(max_size), other) if h >= w else (other, int(max_size))
+
+
+def is_extreme_aspect_ratio(h: int, w: int, max_ratio: float = 5.) -> bool:
+    """longer side / shorter side > max_ratio: the videos the reference's dataset skips before it resizes them
+    (_is_extreme_aspect_ratio, src/datasets/dataset_base.py:224-232)"""
+    return max(h, w) > max_ratio * min(h, w)
+
+
+class RawFrames:
+    """A ragged batch of native-resolution uint8 RGB frames standing for the (B, T, 3, S, S) tensor the reference's collate would
+    have produced from them (S = ``max_img_size``): resized, zero-padded, not yet normalised.
+
+    ``flat``: 1-D uint8, all frames back to back -- interleaved (h, w, 3) each when ``hwc`` (what the decoder hands over before
+    its permute, src/datasets/dataset_base.py:136-146), planar (3, h, w) otherwise.  ``table``: int64 (*lead, 5), one row
+    [byte_offset, h, w, new_h, new_w] per frame, on ``flat``'s device; ``host_table``: the same rows on the host (argument
+    validation at launch time without a device read).  The leading dimensions ``lead`` are the batch dimensions of the tensor
+    it stands for: ``view`` / ``reshape`` / ``transpose`` / indexing / ``contiguous`` act on them exactly as they would on that
+    tensor, by permuting and slicing the TABLE ROWS only -- pixel bytes are never copied on the host, and frames a slice leaves
+    out simply are not referenced any more -- and still travel: ``to`` / ``PrefetchLoader`` upload the WHOLE ``flat`` buffer of a
+    sliced RawFrames (slice on the device, after the copy; re-collate on the host to ship less).  The model consumes it wherever it takes a frame tensor (modeling.cnn_forward)."""
+
+    def __init__(self, flat: torch.Tensor, table: torch.Tensor, max_img_size: int, hwc: bool = True,
+                 host_table: Optional[torch.Tensor] = None):
+        assert flat.dtype == torch.uint8 and flat.dim() == 1
+        assert table.dtype == torch.int64 and table.dim() >= 1 and table.shape[-1] == 5
+        if host_table is None and not table.is_cuda:
+            host_table = table
+        assert host_table is None or (not host_table.is_cuda and host_table.shape == table.shape)
+        self.flat, self.table, self.host_table = flat, table, host_table
+        self.max_img_size, self.hwc = int(max_img_size), bool(hwc)
+
+    def _like(self, table, host_table):
+        return RawFrames(self.flat, table, self.max_img_size, self.hwc, host_table)
+
+    def _both(self, fn):
+        """the same table-row operation on the device table and its host copy"""
+        if self.host_table is None or self.host_table is self.table:
+            t = fn(self.table)
+            return self._like(t, t if self.host_table is not None else None)
+        return self._like(fn(self.table), fn(self.host_table))
+
+    # ---- what the task loops ask of batch["visual_inputs"] --------------------------------------------------------------------
+    @property
+    def shape(self) -> torch.Size:
+        return torch.Size(tuple(self.table.shape[:-1]) + (3, self.max_img_size, self.max_img_size))
+
+    @property
+    def device(self):
+        return self.flat.device
+
+    dtype = torch.uint8
+
+    def dim(self) -> int:
+        return self.table.dim() + 2
+
+    def size(self, d: Optional[int] = None):
+        return self.shape if d is None else self.shape[d]
+
+    def __len__(self):
+        return self.shape[0]
+
+    @property
+    def n_frames(self) -> int:
+        return self.table.numel() // 5
+
+    def _lead(self, shape):
+        if len(shape) == 1 and isinstance(shape[0], (tuple, list, torch.Size)):
+            shape = tuple(shape[0])
+        tail = (3, self.max_img_size, self.max_img_size)
+        if len(shape) < 3 or tuple(int(d) for d in shape[-3:]) != tail:
+            raise ValueError(f"RawFrames: only the leading (batch) dimensions can be regrouped; {tuple(shape)} must end in {tail}")
+        return tuple(int(d) for d in shape[:-3])
+
+    def view(self, *shape):
+        lead = self._lead(shape)
+        return self._both(lambda t: t.view(*lead, 5))
+
+    def reshape(self, *shape):
+        lead = self._lead(shape)
+        return self._both(lambda t: t.reshape(*lead, 5))
+
+    def transpose(self, d0: int, d1: int):
+        nl = self.table.dim() - 1
+        if not (0 <= d0 < nl and 0 <= d1 < nl):
+            raise ValueError("RawFrames: only the leading (batch) dimensions can be transposed")
+        return self._both(lambda t: t.transpose(d0, d1))
+
+    def __getitem__(self, idx):
+        idx = idx if isinstance(idx, tuple) else (idx,)
+        if len(idx) > self.table.dim() - 1 or any(not isinstance(i, (int, slice)) for i in idx):
+            raise IndexError("RawFrames: integer / slice indices over the leading (batch) dimensions only")
+        return self._both(lambda t: t[idx])
+
+    def is_contiguous(self) -> bool:
+        return self.table.is_contiguous()
+
+    def contiguous(self):
+        return self if self.is_contiguous() else self._both(lambda t: t.contiguous())
+
+    def to(self, device, non_blocking: bool = False):
+        device = torch.device(device)
+        host = self.host_table if self.host_table is not None else (self.table if not self.table.is_cuda else None)
+        return RawFrames(self.flat.to(device, non_blocking=non_blocking), self.table.to(device, non_blocking=non_blocking),
+                         self.max_img_size, self.hwc, host)
+
+    def packed_table(self):
+        """(table, host_table) as contiguous (n_frames, 5) row lists in the order of the leading dimensions (what the kernel reads)"""
+        t = self.table.reshape(-1, 5).contiguous()
+        if self.host_table is None:
+            return t, None
+        return t, (t if self.host_table is self.table else self.host_table.reshape(-1, 5).contiguous())
+
+    def __repr__(self):
+        return f"RawFrames(shape={tuple(self.shape)}, bytes={self.flat.numel()}, hwc={self.hwc}, device={self.device})"
+
+
+def collate_raw_frames(videos: Sequence[torch.Tensor], max_img_size: int, hwc: bool = True) -> RawFrames:
+    """The frame half of the reference's collate for frames that were NOT resized by the dataset: ``videos`` holds one uint8 tensor
+    per video, (T, h, w, 3) when ``hwc`` (the decoder's layout) or (T, 3, h, w) otherwise, the same T everywhere, any h x w per
+    video -> the RawFrames standing for the (B, T, 3, S, S) batch.  One concatenation of the bytes; nothing is resized here."""
+    assert len(videos) > 0
+    t0 = videos[0].shape[0]
+    rows, chunks, off = [], [], 0
+    for v in videos:
+        assert v.dtype == torch.uint8 and v.dim() == 4 and v.shape[0] == t0, "every video contributes the same number of uint8 frames"
+        assert v.shape[3 if hwc else 1] == 3, f"expected {'(T, h, w, 3)' if hwc else '(T, 3, h, w)'} frames, got {tuple(v.shape)}"
+        h, w = (v.shape[1], v.shape[2]) if hwc else (v.shape[2], v.shape[3])
+        nh, nw = resize_size(h, w, max_img_size)
+        if min(h, w, nh, nw) < 1:
+            raise ValueError(f"a {h} x {w} frame resizes to {nh} x {nw} at max_img_size {max_img_size} (is_extreme_aspect_ratio videos are skipped by the dataset)")
+        for _ in range(t0):
+            rows.append([off, h, w, nh, nw])
+            off += 3 * h * w
+        chunks.append(v.contiguous().view(-1))
+    table = torch.tensor(rows, dtype=torch.int64).view(len(videos), t0, 5)
+    return RawFrames(torch.cat(chunks), table, max_img_size, hwc)
 
 
 class InfiniteIterator:
@@ -39,7 +190,7 @@ class PrefetchLoader:
 
     ``img_normalize``: ignored as a callable -- pass the model's pixel statistics at model construction instead (frames are
     delivered as uint8 and normalised inside the stem pack).  (task, batch) tuples of the reference's MetaLoader pass
-    through unchanged."""
+    through unchanged.  A ``RawFrames`` anywhere in a batch travels as its two tensors (flat bytes, table) through the same slots."""
 
     def __init__(self, loader: Iterable, device=None, img_normalize=None, slots: int = 2):
         self.loader = loader
@@ -73,6 +224,11 @@ class PrefetchLoader:
         return view.to(self.device, non_blocking=True)  # pinned -> HBM, asynchronous on the side stream
 
     def _move(self, obj, slot, prefix=""):
+        if isinstance(obj, RawFrames):                  # flat bytes and table: two keys of the pinned double buffer
+            table = obj.table.contiguous()
+            host = obj.host_table if obj.host_table is not None else (table if not table.is_cuda else None)
+            return RawFrames(self._move(obj.flat, slot, f"{prefix}/flat"), self._move(table, slot, f"{prefix}/table"),
+                             obj.max_img_size, obj.hwc, host.contiguous() if host is not None else None)
         if torch.is_tensor(obj):
             return self._stage(prefix, slot, obj) if obj.device.type == "cpu" else obj.to(self.device, non_blocking=True)
         if isinstance(obj, dict):
@@ -103,7 +259,11 @@ class PrefetchLoader:
 
     @staticmethod
     def _record_stream(obj, stream):
-        if torch.is_tensor(obj):
+        if isinstance(obj, RawFrames):
+            for t in (obj.flat, obj.table):
+                if t.is_cuda:
+                    t.record_stream(stream)
+        elif torch.is_tensor(obj):
             if obj.is_cuda:
                 obj.record_stream(stream)
         elif isinstance(obj, dict):

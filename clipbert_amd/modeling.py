@@ -24,6 +24,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .data import RawFrames
 from .ops import (ACT_GELU, ACT_NONE, ACT_RELU, ACT_TANH, KROW, KROW_GATHER, KROW_TAPS, ROWK, ROWK_GATHER)
 
 from .params import ParamBank
@@ -351,27 +352,39 @@ def _res2_fusable(rt: Runtime, x, blk: BottleneckBlock, save: bool) -> bool:
 
 
 def cnn_forward(bb: "GridFeatBackbone", x5: torch.Tensor, save: bool):
-    """(B,T,3,H,W) fp32 RGB mean-subtracted (or uint8 RGB) -> grid (B,T,H',W',hidden) + saved activations."""
+    """(B,T,3,H,W) fp32 RGB mean-subtracted (or uint8 RGB), or the RawFrames standing for such a batch (native-resolution uint8
+    frames: resized, padded and normalised here) -> grid (B,T,H',W',hidden) + saved activations."""
     rt = bb.rt
     b, t, c, h, w = x5.shape
     n = b * t
-    x4 = x5.reshape(n, c, h, w)
-    if not x4.is_contiguous():
-        x4 = x4.contiguous()
+    raw = isinstance(x5, RawFrames)
+    if raw:
+        # ImageResize + ImagePad + ImageNorm + BGR flip of the whole ragged batch in one launch, straight into the stem's packed image
+        table, host_table = x5.packed_table()
+        packed_raw = ops.resize_pack_u8(x5.flat, table, n, h, rt.dtype, bb.pixel_mean, bb.pixel_std, hwc=x5.hwc, pad=3, extra_w=2,
+                                        host_table=host_table)
+    else:
+        x4 = x5.reshape(n, c, h, w)
+        if not x4.is_contiguous():
+            x4 = x4.contiguous()
     net = bb.feature.backbone
     stem = net.stem.conv1
     oh, ow = (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1
     m = n * oh * ow
     scale, shift = stem.scale_shift()
     fuse_stem = rt.dtype == torch.bfloat16 and w % 2 == 0
-    if x4.dtype == torch.uint8 and fuse_stem:
+    if raw and fuse_stem:
+        x = ops.stem_pool(packed_raw, _stem_weight(rt, stem), scale, shift, oh, ow)
+    elif not raw and x4.dtype == torch.uint8 and fuse_stem:
         # uint8 frames straight into the first convolution: ImageNorm, BGR flip and padding inside cb_stem_pool's tile loader (round 6, N4)
         x = ops.stem_pool_u8(x4, bb.pixel_mean, bb.pixel_std, _stem_weight(rt, stem), scale, shift)
     elif fuse_stem:
         # convolution + FrozenBN + ReLU + max-pool in one launch (the 112 x 112 x 64 map never leaves the CU)
         x = ops.stem_pool(ops.stem_pack(x4.float(), rt.dtype, 3, extra_w=2), _stem_weight(rt, stem), scale, shift, oh, ow)
     else:
-        if x4.dtype == torch.uint8:
+        if raw:
+            packed = packed_raw
+        elif x4.dtype == torch.uint8:
             packed = ops.stem_pack(x4, rt.dtype, 3, bb.pixel_mean, bb.pixel_std, extra_w=2)
         else:
             packed = ops.stem_pack(x4.float(), rt.dtype, 3, extra_w=2)
@@ -517,7 +530,7 @@ class GridFeatBackbone(nn.Module):
         return any(p.requires_grad for p in self.parameters())
 
     def forward(self, x):
-        """x: (B, n_frm, 3, H, W) RGB float (mean-subtracted) or uint8 -> (B, n_frm, H', W', hidden)."""
+        """x: (B, n_frm, 3, H, W) RGB float (mean-subtracted) or uint8, or a data.RawFrames of that shape -> (B, n_frm, H', W', hidden)."""
         return _CnnFn.apply(self.rt.anchor, x, self)
 
 
@@ -1403,7 +1416,7 @@ class ClipBert(nn.Module):
             self.prepare(device=device)
 
     def grid_features(self, visual_inputs):
-        """(Bv, T, 3, H, W) frames -> (Bv, T, H', W', hidden) grid features: the CNN half of forward() on its own, so that
+        """(Bv, T, 3, H, W) frames (tensor or data.RawFrames) -> (Bv, T, H', W', hidden) grid features: the CNN half of forward() on its own, so that
         inference can compute each clip's features once and reuse them across text mini-batches (SURVEY 8f N1;
         the reference recomputes them per mini-batch, run_video_retrieval.py:655-666)."""
         self._ensure_prepared(visual_inputs.device)

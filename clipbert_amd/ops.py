@@ -227,6 +227,24 @@ def stem_pack(src: torch.Tensor, dtype: torch.dtype, pad: int = 3, mean=None, st
     return dst
 
 
+def resize_pack_u8(flat_u8: torch.Tensor, table: torch.Tensor, n: int, size: int, dtype: torch.dtype, mean, std, hwc: bool = True,
+                   pad: int = 3, extra_w: int = 0, host_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cb_resize_pack_u8: ``n`` native-resolution uint8 RGB frames lying back to back in ``flat_u8`` -> the reference's bilinear
+    resize (longer side -> ``size``) + zero pad to size x size + ImageNorm, as stem_pack's (n, size+2*pad, size+2*pad+extra_w, 4)
+    BGR0 image.  ``table``: int64 (n, 5) rows [byte_offset, h, w, new_h, new_w] on flat_u8's device (clipbert_amd.data.RawFrames
+    builds it); ``host_table``: a CPU copy whose rows the library validates before the launch.  One launch, no host sync."""
+    assert flat_u8.dtype == torch.uint8 and flat_u8.dim() == 1 and flat_u8.is_contiguous()
+    assert table.dtype == torch.int64 and tuple(table.shape) == (n, 5) and table.is_contiguous() and table.device == flat_u8.device
+    if host_table is not None:
+        assert host_table.dtype == torch.int64 and tuple(host_table.shape) == (n, 5) and host_table.is_contiguous() and not host_table.is_cuda
+    hp, wp = size + 2 * pad, size + 2 * pad + extra_w
+    dst = torch.empty(n, hp, wp, 4, dtype=dtype, device=flat_u8.device)
+    _chk(_lib.get().cb_resize_pack_u8(dtype_code(dtype), _ptr(flat_u8), flat_u8.numel(), _ptr(table),
+                                      host_table.data_ptr() if host_table is not None else None, n, int(hwc), _f3(mean), _f3(std),
+                                      _ptr(dst), size, hp, wp, pad, _stream(flat_u8)), "cb_resize_pack_u8")
+    return dst
+
+
 def image_norm(frames_u8: torch.Tensor, mean, std) -> torch.Tensor:
     """ImageNorm (a1): uint8 (..., 3, H, W) -> fp32."""
     assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous() and frames_u8.shape[-3] == 3

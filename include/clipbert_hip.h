@@ -199,6 +199,26 @@ int cb_stem_pack(int32_t dtype, const void* src, int32_t src_u8, const float* me
                  void* dst, int32_t N, int32_t H, int32_t W, int32_t Hp, int32_t Wp, int32_t pad,
                  void* stream);
 
+/* Raw-frame ingest: the reference's per-frame ImageResize(max_img_size, "bilinear") + ImagePad(max_img_size, max_img_size)
+ * (src/datasets/data_utils.py:112-253, applied by _load_video, src/datasets/dataset_base.py:270-273) + ImageNorm + the RGB -> BGR flip,
+ * from the decoder's native-resolution uint8 frames, for a RAGGED batch of N frames in one launch.
+ *   flat / flat_bytes : one device buffer with all frames back to back, RGB; hwc = 1: interleaved (h, w, 3), what the decoder hands
+ *                       over before its permute (dataset_base.py:136-146); hwc = 0: planar (3, h, w)
+ *   table             : DEVICE, N rows of five int64 [byte_offset, h, w, new_h, new_w]; new_h x new_w is get_resize_size's result
+ *                       (data_utils.py:167-199: longer side -> S).  Read by the kernel only: a launch with fixed (N, S) needs no host
+ *                       synchronisation and can be captured into a hipGraph.  A row that does not describe a frame inside the buffer
+ *                       (sizes < 1, new size > S, bytes past flat_bytes) reads nothing and yields an all-padding frame.
+ *   table_host        : optional HOST copy of the table (NULL: not checked); its rows are validated before the launch
+ *   dst               : exactly cb_stem_pack's image: (N, Hp, Wp, 4) of dtype, channels B, G, R, 0, Hp, Wp >= S + 2 * pad.  Inside
+ *                       new_h x new_w: the bilinear sample (PyTorch upsample_bilinear2d, align_corners = False, no antialiasing, fp32
+ *                       on the raw 0..255 values; the source coordinate is ONE fused multiply-add), then (v - mean[c]) * (1 / std[c]);
+ *                       inside S x S beyond it: ImagePad's zero pixel, normalised the same way (the reference pads before it
+ *                       normalises); outside S x S: zeros.  A frame with (h, w) == (new_h, new_w) equals cb_stem_pack(src_u8 = 1) bit
+ *                       for bit.  mean3 / std3: HOST arrays of 3 floats (RGB order). */
+int cb_resize_pack_u8(int32_t dtype, const uint8_t* flat, int64_t flat_bytes, const int64_t* table, const int64_t* table_host, int32_t N,
+                      int32_t hwc, const float* mean3, const float* std3, void* dst, int32_t S, int32_t Hp, int32_t Wp, int32_t pad,
+                      void* stream);
+
 /* ImageNorm alone (a1): uint8 (n) -> fp32 (x - mean[c]) / std[c], NCHW with plane size hw.
  * mean3 / std3: HOST arrays of 3 floats. */
 int cb_image_norm(const uint8_t* src, float* dst, const float* mean3, const float* std3,
@@ -421,7 +441,8 @@ const char* cb_last_error(void);
  * 6 = cb_gemm_desc grew by sq_slots / sq_slots_n at its END (zero = off: older callers that memset the struct they allocate with the
  *     new size are unaffected), accumulate = 2 (first writer), cb_sq_sum_fold;
  * 7 = cb_gemm_desc.tile = 9 (few rows), chosen by itself for M <= 64: the same result up to the order of the fp32 additions;
- *     cb_gemm_group takes strided batches / a_rowsum on the unsplit bf16 weight-gradient form; cb_stem_pool_u8; cb_zero_ranges */
+ *     cb_gemm_group takes strided batches / a_rowsum on the unsplit bf16 weight-gradient form; cb_stem_pool_u8; cb_zero_ranges;
+ * 8 = cb_resize_pack_u8 (raw-frame ingest: resize + pad + ImageNorm of native-resolution uint8 frames; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
