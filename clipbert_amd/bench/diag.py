@@ -36,7 +36,7 @@ def build(ctx):
             bank.zero_grad_range(0, t_end, lazy=True)                        # ... then its gradients may go
         bank.begin_epoch(lazy=True)                                          # (the lazy span is written by this step's encoder backward)
         bank.zero_grad_range(t_end, bank.grad.numel())
-        model.rt.pending_encoder_nodes = model.rt.pending_cnn_nodes = 0
+        model.rt.begin_step()
         vis = frames.view(bv * nclip, T, *frames.shape[2:]) if (fold and nclip > 1) else frames
         grid = model.grid_features(vis)                                      # ResNet forward beside the deferred update
         cur.wait_stream(pipe_stream)

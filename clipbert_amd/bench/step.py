@@ -92,7 +92,7 @@ def make_step(model, batch, tcfg, opt, sync, labels, counts, n_clips, frames, po
     def device_step():
         """everything a 1-GPU step enqueues (capturable)"""
         opt.zero_grad(lazy=True)
-        model.rt.pending_encoder_nodes = model.rt.pending_cnn_nodes = 0
+        model.rt.begin_step()
         loss = forward_loss()
         loss.backward(one)
         ops.counter_add(model.rt.seed_dev)

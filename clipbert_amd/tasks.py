@@ -120,8 +120,7 @@ def train_step(model, optimizer, batch: Dict, cfg, global_step: int, sync=None, 
     if first:
         optimizer.zero_grad(lazy=True)                      # a backward always follows: the encoder weight gradients are overwritten
     rt = model.rt
-    rt.pending_encoder_nodes = 0
-    rt.pending_cnn_nodes = 0
+    rt.begin_step()
     hook, hook5 = rt.after_encoder_backward, rt.after_res5_backward
     if not last:
         rt.after_encoder_backward = None                    # no exchange before the group is complete

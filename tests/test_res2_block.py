@@ -76,6 +76,7 @@ def test_res2_block_equals_the_block_op_by_op(hw, monkeypatch, cin, n, h, w, max
 def test_fused_block_equals_the_unfused_product_path(hw, first):
     """the model's own modules: ops.res2_block against the three / four cb_gemm launches of modeling._conv_fwd on the same block"""
     from clipbert_amd import modeling as M
+    from clipbert_amd.modeling import cnn as C
     from clipbert_amd import synthetic as S
     from oracle import clipbert_oracle as O
     cfg = dict(O.BASE_CONFIG, num_hidden_layers=1, num_labels=2, loss_type="ce", margin=0.1, vocab_size=300, max_position_embeddings=40)
@@ -87,11 +88,11 @@ def test_fused_block_equals_the_unfused_product_path(hw, first):
     blk = model.cnn.feature.backbone.res2[0 if first else 1]
     cin = 64 if first else 256
     x = (torch.randn(2, 16, 24, cin, generator=_gen(11))).relu().to(torch.bfloat16).to(DEV[0])
-    sc = M._conv_fwd(rt, x, blk.shortcut) if blk.shortcut is not None else x
-    y1 = M._conv_fwd(rt, x, blk.conv1, act=M.ACT_RELU)
-    y2 = M._conv_fwd(rt, y1, blk.conv2, act=M.ACT_RELU)
-    ref = M._conv_fwd(rt, y2, blk.conv3, residual=sc, relu_after=True)
-    got = M._res2_block_fused(rt, x, blk)
+    sc = C._conv_fwd(rt, x, blk.shortcut) if blk.shortcut is not None else x
+    y1 = C._conv_fwd(rt, x, blk.conv1, act=M.ACT_RELU)
+    y2 = C._conv_fwd(rt, y1, blk.conv2, act=M.ACT_RELU)
+    ref = C._conv_fwd(rt, y2, blk.conv3, residual=sc, relu_after=True)
+    got = C._res2_block_fused(rt, x, blk)
     err = (got.float() - ref.float()).abs()
     assert float(err.max()) <= 2 ** -7 * max(1.0, float(ref.float().abs().max())), float(err.max())
     assert float((err > 0).float().mean()) < 0.05

@@ -147,10 +147,10 @@ CONVS = [  # (name, cin, cout, k, stride, H_in) at 64 frames of 224 px
 
 def conv_rows(nframes=64):
     """MIOpen (NHWC bf16, immediate mode) forward / input gradient / weight gradient next to the product's launches of the same
-    convolutions (clipbert_amd.modeling._conv_fwd / _conv_dgrad / _conv_wgrad: FrozenBN scale + shift in the forward epilogue, which
+    convolutions (clipbert_amd.modeling.cnn._conv_fwd / _conv_dgrad / _conv_wgrad: FrozenBN scale + shift in the forward epilogue, which
     the library call does not do)"""
     from clipbert_amd.bench import step as bench_step
-    from clipbert_amd import modeling as Mo
+    from clipbert_amd.modeling import cnn as Mo
     st = bench_step.build(videos=2)
     model, rt = st.model, st.model.rt
     bb = model.cnn.feature.backbone

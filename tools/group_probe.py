@@ -85,7 +85,7 @@ def main():
     dev = torch.device("cuda", 0)
     flush = torch.zeros(128 << 20, device=dev)                       # 512 MB read-modify-write: nothing of the operands stays cached
     import math
-    from clipbert_amd.modeling import _pick_split
+    from clipbert_amd.modeling.runtime import _pick_split
     res = {}
     for name in STAGES:
         probs, m = stage_problems(name, args.frames, dev)

@@ -9,7 +9,7 @@ from gemm_yardstick import hot_cold
 
 def main():
     from clipbert_amd.bench import step as bench_step
-    from clipbert_amd import modeling as M
+    from clipbert_amd.modeling import cnn as M
     st = bench_step.build(videos=2)
     rt = st.model.rt
     res2 = st.model.cnn.feature.backbone.res2
