@@ -15,6 +15,7 @@ SPLITK_WS_COUNTER_BYTES = 65536                     # CB_SPLITK_WS_COUNTER_BYTES
 ACT_GELU_SAVE_GRAD, ACT_SAVED_GRAD = 4, 5          # cb_gemm only: GELU with C2 = gelu'(pre); backward multiplies by that stored derivative
 ROWK, ROWK_GATHER, KROW, KROW_TAPS, KROW_GATHER = 0, 1, 2, 3, 4
 (HP_LR, HP_BETA1, HP_BETA2, HP_EPS, HP_WD, HP_BC1, HP_BC2, HP_MAX_NORM, HP_GRAD_SCALE, HP_SKIP, HP_COUNT) = range(11)
+OPT_ADAMW, OPT_ADAM, OPT_ADAMAX = 0, 1, 2          # CB_OPT_*: the algo of cb_optim_step
 
 vp, i32, i64, f32, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 
@@ -97,6 +98,7 @@ _SIGNATURES = {
     "cb_sq_sum_det": [vp, i64, vp, vp, i32, vp],
     "cb_sq_sum_det_bf16": [vp, i64, vp, vp, i32, vp],
     "cb_adamw_g16": [vp, vp, vp, vp, vp, i64, vp, vp, vp],
+    "cb_optim_step": [i32, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp],
     "cb_elu_bn1d_fwd": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp],
     "cb_elu_bn1d_bwd": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
 }

@@ -3,7 +3,8 @@
 * ``ModelSaver`` / ``E2E_TrainingRestorer``: the saver and the resume file of src/utils/load_save.py:43-68,245-312 --
   ``model_step_N.pt`` is a plain CPU state dict with the REFERENCE's key layout (our modules use the same names and the
   same logical OIHW conv shapes, so a file written here loads into the reference and vice versa);
-  ``model_step_N_train_state.pt`` / ``restore.pt`` carry the optimizer state of clipbert_amd.optim.FusedAdamW.
+  ``model_step_N_train_state.pt`` / ``restore.pt`` carry the optimizer state of clipbert_amd.optim.FusedAdamW / FusedAdam / FusedAdamax
+  (whichever cfg.optim built; the state dict names its "algo" and refuses to load into another one).
 * ``load_detectron2_backbone``: what DetectionCheckpointer(self.feature).resume_or_load does for ClipBERT's use of it
   (src/modeling/grid_feat.py:72-80): a detectron2 ``.pth`` (``{"model": {...}}``, keys ``backbone.*``, RPN / ROI heads
   ignored), a detectron2 model-zoo ``.pkl`` (numpy arrays, same keys or the Caffe2-era names are NOT handled), or a
@@ -15,8 +16,8 @@ model's load_state_dict hook.
 Ranks (the reference: restore on EVERY rank, then saver / restorer replaced by NoOp on ranks != 0, run_video_retrieval.py:
 329-346): build ``ModelSaver`` and ``E2E_TrainingRestorer`` on every rank; both write on rank 0 only, the restorer reads on
 all ranks.  File formats: ``model_step_N.pt`` is interchangeable with the reference; ``*_train_state.pt`` / ``restore.pt``
-hold clipbert_amd.optim.FusedAdamW's own state dict (moments keyed by parameter NAME) plus the dropout counters of the
-runtime -- not loadable by the reference's AdamW, and vice versa."""
+hold the fused optimizer's own state dict (moments keyed by parameter NAME) plus the dropout counters of the
+runtime -- not loadable by the reference's optimizer classes, and vice versa."""
 import os
 import pickle
 from typing import Any, Dict, Optional

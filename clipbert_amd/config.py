@@ -121,10 +121,12 @@ def setup_model(cfg: Config, device=None, dtype=torch.bfloat16, config_root: Opt
 
 
 def setup_optimizer(model, cfg: Config):
-    """setup_e2e_optimizer (src/optimization/utils.py:96-128): AdamW over the 8 groups with the config's rates."""
-    from .optim import FusedAdamW
-    if cfg.optim != "adamw":
-        raise ValueError("invalid optimizer" if cfg.optim not in ("adam", "adamax") else f"optimizer {cfg.optim} is not built (adamw is)")
-    return FusedAdamW(model.rt.bank, lr=cfg.learning_rate, betas=tuple(cfg.betas), weight_decay=cfg.weight_decay,
-                      cnn_lr=cfg.cnn_learning_rate, cnn_weight_decay=cfg.cnn_weight_decay, transformer_lr_mul=cfg.transformer_lr_mul,
-                      cnn_lr_mul=cfg.cnn_lr_mul, max_grad_norm=cfg.grad_norm)
+    """setup_e2e_optimizer (src/optimization/utils.py:96-128): cfg.optim picks AdamW, Adam or Adamax over the 8 groups with the config's
+    rates (cnn_optim is not consulted there either)."""
+    from . import optim
+    classes = dict(adamw=optim.FusedAdamW, adam=optim.FusedAdam, adamax=optim.FusedAdamax)
+    if cfg.optim not in classes:
+        raise ValueError("invalid optimizer")
+    return classes[cfg.optim](model.rt.bank, lr=cfg.learning_rate, betas=tuple(cfg.betas), weight_decay=cfg.weight_decay,
+                              cnn_lr=cfg.cnn_learning_rate, cnn_weight_decay=cfg.cnn_weight_decay, transformer_lr_mul=cfg.transformer_lr_mul,
+                              cnn_lr_mul=cfg.cnn_lr_mul, max_grad_norm=cfg.grad_norm)

@@ -1,5 +1,5 @@
-// Fused AdamW over flat fp32 ranges with on-device global-norm clipping (no host sync), optionally
-// emitting the bf16 compute copy of the updated weights in the same pass.  HBM-bound:
+// Fused AdamW (and the reference's other two `optim` choices, Adam and Adamax) over flat fp32 ranges with on-device global-norm
+// clipping (no host sync), optionally emitting the bf16 compute copy of the updated weights in the same pass.  HBM-bound:
 // 4 reads + 3 writes of fp32 (+ 1 bf16 write) per parameter.
 #include "common.h"
 
@@ -172,6 +172,75 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* p, const G* g, float*
 
 // non-temporal fp32 state traffic (round 3, profiles/r03p_adamw_nt.txt: 6.09 -> 6.38 TB/s on a 96 M-element range)
 constexpr bool adamw_nt() { return true; }
+
+// torch.optim.Adam (no amsgrad) and torch.optim.Adamax, the other two classes setup_e2e_optimizer instantiates (src/optimization/utils.py:
+// 96-128).  Both put the weight decay on the GRADIENT (L2, before the moments) and divide lr by bc1 only; `sc` is lr / bc1.
+//   Adam:   v = b2 v + (1 - b2) g^2,      p -= sc * m / (sqrt(v) / sqrt(bc2) + eps)       (`aux` = sqrt(bc2))
+//   Adamax: u = max(b2 u, |g| + eps),     p -= sc * m / u                                 (u lives where v does)
+template <int ALGO>
+__device__ __forceinline__ PMV adam_family_one(float p, float g, float m, float v, float gs, float b1, float b2, float eps, float sc,
+                                               float wd, float aux) {
+    g *= gs;
+    if (wd != 0.f) g += wd * p;
+    m = m * b1 + (1.0f - b1) * g;
+    float denom;
+    if constexpr (ALGO == CB_OPT_ADAM) {
+        v = v * b2 + (1.0f - b2) * g * g;
+        denom = sqrtf(v) / aux + eps;
+    } else {
+        v = fmaxf(v * b2, fabsf(g) + eps);
+        denom = v;
+    }
+    p = p - sc * (m / denom);
+    PMV r = {p, m, v};
+    return r;
+}
+
+// Same structure as adamw_kernel (always with the non-temporal state traffic): 30 bytes per parameter, one f32x4 chunk per thread.
+template <typename G, int ALGO>
+__global__ void __launch_bounds__(256) adam_family_kernel(float* p, const G* g, float* m, float* v, bf16* w16, int64_t n,
+                                                          const float* hp, const float* sq_sum) {
+    if (hp[CB_HP_SKIP] != 0.f) return;                   // (block-uniform: every thread reads the same word)
+    const float b1 = hp[CB_HP_BETA1], b2 = hp[CB_HP_BETA2], eps = hp[CB_HP_EPS];
+    const float wd = hp[CB_HP_WD], max_norm = hp[CB_HP_MAX_NORM];
+    const float sc = hp[CB_HP_LR] / hp[CB_HP_BC1];
+    const float aux = ALGO == CB_OPT_ADAM ? sqrtf(hp[CB_HP_BC2]) : 0.f;
+    float gs = hp[CB_HP_GRAD_SCALE];
+    if (sq_sum && max_norm > 0.f) {
+        float total = sqrtf(*sq_sum) * gs;
+        float coef = max_norm / (total + 1e-6f);
+        gs *= coef < 1.0f ? coef : 1.0f;
+    }
+    int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    if (i + 3 < n) {
+        const f32x4 gg = load4(g + i);
+        f32x4 pp = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p + i));
+        f32x4 mm = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(m + i));
+        f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(v + i));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            PMV r = adam_family_one<ALGO>(pp[e], gg[e], mm[e], vv[e], gs, b1, b2, eps, sc, wd, aux);
+            pp[e] = r.p; mm[e] = r.m; vv[e] = r.v;
+        }
+        __builtin_nontemporal_store(pp, reinterpret_cast<f32x4*>(p + i));
+        __builtin_nontemporal_store(mm, reinterpret_cast<f32x4*>(m + i));
+        __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v + i));
+        if (w16) store4(w16 + i, pp);
+    } else {
+        for (; i < n; ++i) {
+            PMV r = adam_family_one<ALGO>(p[i], to_f32(g[i]), m[i], v[i], gs, b1, b2, eps, sc, wd, aux);
+            p[i] = r.p; m[i] = r.m; v[i] = r.v;
+            if (w16) w16[i] = (bf16)r.p;
+        }
+    }
+}
+
+template <typename G, int ALGO>
+void launch_adam_family(float* p, const void* g, float* m, float* v, void* w16, int64_t n, const float* hyper, const float* sq_sum, void* stream) {
+    hipLaunchKernelGGL((adam_family_kernel<G, ALGO>), dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, cb_stream(stream), p, (const G*)g, m, v,
+                       (bf16*)w16, n, hyper, sq_sum);
+}
 }  // namespace
 
 extern "C" int cb_sq_sum(const float* g, int64_t n, float* out_accum, void* stream) {
@@ -252,4 +321,20 @@ extern "C" int cb_adamw(float* p, const float* g, float* m, float* v, void* w16,
         hipLaunchKernelGGL((adamw_kernel<float, false>), dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, cb_stream(stream), p, g, m, v, (bf16*)w16, n,
                            hyper, grad_sq_sum);
     return cb_launch_status("cb_adamw");
+}
+
+extern "C" int cb_optim_step(int32_t algo, int32_t grad_dtype, float* p, const void* g, float* m, float* v2, void* w16, int64_t n, const float* hyper,
+                             const float* grad_sq_sum, void* stream) {
+    CB_REQUIRE(algo == CB_OPT_ADAMW || algo == CB_OPT_ADAM || algo == CB_OPT_ADAMAX, "cb_optim_step: unknown algo %d", (int)algo);
+    CB_REQUIRE(grad_dtype == CB_F32 || grad_dtype == CB_BF16, "cb_optim_step: grad_dtype %d is neither CB_F32 nor CB_BF16", (int)grad_dtype);
+    CB_REQUIRE(p && g && m && v2 && hyper, "cb_optim_step: null pointer");
+    const bool g16 = grad_dtype == CB_BF16;
+    if (algo == CB_OPT_ADAMW)
+        return g16 ? cb_adamw_g16(p, g, m, v2, w16, n, hyper, grad_sq_sum, stream) : cb_adamw(p, (const float*)g, m, v2, w16, n, hyper, grad_sq_sum, stream);
+    if (n == 0) return 0;
+    if (algo == CB_OPT_ADAM)
+        (g16 ? launch_adam_family<bf16, CB_OPT_ADAM> : launch_adam_family<float, CB_OPT_ADAM>)(p, g, m, v2, w16, n, hyper, grad_sq_sum, stream);
+    else
+        (g16 ? launch_adam_family<bf16, CB_OPT_ADAMAX> : launch_adam_family<float, CB_OPT_ADAMAX>)(p, g, m, v2, w16, n, hyper, grad_sq_sum, stream);
+    return cb_launch_status("cb_optim_step");
 }

@@ -8,7 +8,7 @@ out transformer-groups-first, so the exchange is two large bucket all-reduces:
              xGMI on RCCL's side stream WHILE the ResNet backward (the larger half of the step) runs;
   bucket 1 = CNN parameters: issued after the CNN backward.
 
-Sums are averaged inside the fused AdamW (grad_scale = 1/world), so no extra pass touches the buffer.
+Sums are averaged inside the fused optimizer update (FusedAdamW / FusedAdam / FusedAdamax: grad_scale = 1/world), so no extra pass touches the buffer.
 The dead detectron2 RPN/ROI parameters the reference also all-reduces do not exist here.
 """
 from typing import List, Optional
@@ -209,7 +209,7 @@ class GradSync:
         self.loopback = bool(loopback) and self.world == 1 and not self.dry
         if self.world > 1 or self.loopback or self.dry:
             # the gradient norm of a data-parallel step is the norm of the EXCHANGED gradients: the per-launch shares of the local ones
-            # (ParamBank.enable_norm_fold) say nothing about it -- FusedAdamW.launch runs its pass over the reduced gradients
+            # (ParamBank.enable_norm_fold) say nothing about it -- the optimizer's launch() (FusedAdamW and its Adam / Adamax subclasses) runs its pass over the reduced gradients
             bank.block_norm_fold()
         t_end = bank.group_range[3][1]
         self.t_range = (0, t_end)

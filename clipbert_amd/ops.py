@@ -587,6 +587,13 @@ def adamw(p, g, m, v, w16, hyper_dev, grad_sq_sum=None):
                              _ptr(grad_sq_sum), _stream(p)), "cb_adamw")
 
 
+def optim_step(algo, p, g, m, v2, w16, hyper_dev, grad_sq_sum=None):
+    """cb_optim_step: ``algo`` = _lib.OPT_ADAMW | OPT_ADAM | OPT_ADAMAX on one flat range; arguments as ``adamw`` (v2: exp_avg_sq, or Adamax's
+    exp_inf).  g: fp32 or bf16."""
+    _chk(_lib.get().cb_optim_step(algo, dtype_code(g.dtype), _ptr(p), _ptr(g), _ptr(m), _ptr(v2), _ptr(w16), p.numel(), _ptr(hyper_dev),
+                                  _ptr(grad_sq_sum), _stream(p)), "cb_optim_step")
+
+
 def dropout(x, p, seed=0, seed_ptr=None, out=None):
     y = torch.empty_like(x) if out is None else out
     _chk(_lib.get().cb_dropout(dtype_code(x.dtype), _ptr(x), _ptr(y), x.numel(), p, seed, _ptr(seed_ptr), _stream(x)),

@@ -1,9 +1,11 @@
-"""Fused AdamW over the flat parameter buffers + the reference's LR schedule.
+"""Fused AdamW / Adam / Adamax over the flat parameter buffers + the reference's LR schedule.
 
-Semantics follow src/optimization/adamw.py:40-103 (eps 1e-6, bias correction, decoupled weight decay
-applied after the Adam update with the un-corrected lr), the 8 param groups of
-src/optimization/utils.py:96-161 and the global-norm clipping of run_video_retrieval.py:477-482.
-One ``cb_sq_sum`` + one ``cb_adamw`` launch per non-empty group; hyper-parameters travel through a
+FusedAdamW follows src/optimization/adamw.py:40-103 (eps 1e-6, bias correction, decoupled weight decay
+applied after the Adam update with the un-corrected lr); FusedAdam and FusedAdamax are torch.optim.Adam
+(no amsgrad) and torch.optim.Adamax, the other two classes cfg.optim selects in
+src/optimization/utils.py:96-128 (eps 1e-8, L2 weight decay on the gradient).  All three share the 8 param
+groups of src/optimization/utils.py:96-161 and the global-norm clipping of run_video_retrieval.py:477-482.
+One ``cb_sq_sum`` + one update launch per non-empty group; hyper-parameters travel through a
 small DEVICE array so a captured hipGraph replays with fresh lr / step / clip values.
 """
 from typing import List, Optional, Sequence
@@ -11,7 +13,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
-from ._lib import HP_COUNT, HP_SKIP
+from ._lib import HP_COUNT, HP_SKIP, OPT_ADAM, OPT_ADAMAX, OPT_ADAMW
 from .params import N_GROUPS, ParamBank
 
 
@@ -52,9 +54,13 @@ def get_lr_sched(global_step: int, decay: str, learning_rate: float, num_train_s
 
 class FusedAdamW:
     """``param_groups`` mirrors the reference list (8 dicts with 'lr' and 'weight_decay') so runner code
-    that assigns ``optimizer.param_groups[i]['lr']`` (run_video_retrieval.py:455-467) works unchanged."""
+    that assigns ``optimizer.param_groups[i]['lr']`` (run_video_retrieval.py:455-467) works unchanged.
 
-    def __init__(self, bank: ParamBank, lr: float = 5e-5, betas=(0.9, 0.98), eps: float = 1e-6, weight_decay: float = 1e-3,
+    Also the base of FusedAdam / FusedAdamax: they differ in the update kernel (``_update``), the default eps and the names in the
+    state dict (``algo`` / ``second_key``) only."""
+    algo, algo_code, second_key, default_eps = "adamw", OPT_ADAMW, "exp_avg_sq", 1e-6
+
+    def __init__(self, bank: ParamBank, lr: float = 5e-5, betas=(0.9, 0.98), eps: Optional[float] = None, weight_decay: float = 1e-3,
                  cnn_lr: Optional[float] = None, cnn_weight_decay: Optional[float] = None, transformer_lr_mul: float = 1.0,
                  cnn_lr_mul: float = 1.0, max_grad_norm: float = -1.0, fold_norm: bool = True):
         """fold_norm: after ``zero_grad(lazy=True)`` the weight-gradient launches leave their shares of the squared gradient norm in slots
@@ -63,7 +69,7 @@ class FusedAdamW:
         self.bank = bank
         bank.clients += 1
         bank.ensure_state()
-        self.betas, self.eps = betas, eps
+        self.betas, self.eps = betas, self.default_eps if eps is None else eps
         self.max_grad_norm = max_grad_norm
         cnn_lr = lr if cnn_lr is None else cnn_lr
         cnn_wd = weight_decay if cnn_weight_decay is None else cnn_weight_decay
@@ -107,7 +113,7 @@ class FusedAdamW:
         and enqueue their (tiny) H2D copy on the current stream.  Never captured into a hipGraph: a training loop that
         replays a captured step calls ``prepare_step()`` eagerly before each replay and captures only ``launch()``."""
         if self._hp_dev.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("FusedAdamW.prepare_step() inside a hipGraph capture: capture launch() only and call "
+            raise RuntimeError(f"{type(self).__name__}.prepare_step() inside a hipGraph capture: capture launch() only and call "
                                "prepare_step() eagerly before each replay (see INTEGRATION.md)")
         if self.deferred_pending and self.step_count > 0:      # an update was left behind by the step before: it needs that step's values
             self._hp_dev_prev.copy_(self._hp_dev)              # D2D, stream-ordered before the upload below overwrites _hp_dev
@@ -135,7 +141,7 @@ class FusedAdamW:
     @torch.no_grad()
     def launch(self, grad16: Optional[torch.Tensor] = None, groups: Optional[Sequence[int]] = None, prev: bool = False,
                reuse_norm: bool = False, pieces=None, norm_reduce=None):
-        """Device half of a step (capturable): global grad-norm reduction, then clip + AdamW + bf16 weight refresh, reading
+        """Device half of a step (capturable): global grad-norm reduction, then clip + update + bf16 weight refresh, reading
         the hyper-parameters from the device array prepare_step() filled.  ``grad16``: consume these bf16 gradients (flat, same
         layout as bank.grad -- GradSync's reduced wire image, ``sync.wire_gradients()``) instead of the fp32 buffer.
 
@@ -179,7 +185,10 @@ class FusedAdamW:
             spans = [(a, b)] if pieces is None else [(max(a, lo), min(b, hi)) for lo, hi in pieces if lo < b and a < hi]
             for x, y in spans:
                 w16 = bank.w16[x:y] if bank.w16 is not None else None
-                ops.adamw(bank.master[x:y], gsrc[x:y], bank.exp_avg[x:y], bank.exp_avg_sq[x:y], w16, hp_dev[g], sq)
+                self._update(bank.master[x:y], gsrc[x:y], bank.exp_avg[x:y], bank.exp_avg_sq[x:y], w16, hp_dev[g], sq)
+
+    def _update(self, p, g, m, v2, w16, hp, sq):
+        ops.adamw(p, g, m, v2, w16, hp, sq)
 
     def step(self, grad_scale: float = 1.0, grad16: Optional[torch.Tensor] = None, pieces=None, norm_reduce=None):
         """grad_scale multiplies the gradients first (1/world_size after a SUM all-reduce)."""
@@ -192,24 +201,29 @@ class FusedAdamW:
 
     # ---- checkpointing (the reference saves optimizer.state_dict() in *_train_state.pt / restore.pt) ------------------
     def state_dict(self) -> dict:
-        """{"state": {parameter name: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...], "step": n}: moments in the
-        parameters' LOGICAL shapes (OIHW for convs), keyed by name so that the file does not depend on the flat layout."""
+        """{"state": {parameter name: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [...], "step": n, "algo": "adamw" | "adam" |
+        "adamax"}: moments in the parameters' LOGICAL shapes (OIHW for convs), keyed by name so that the file does not depend on the
+        flat layout.  Adamax's second state goes by torch's name for it, "exp_inf"."""
         bank = self.bank
-        bank.assert_whole("FusedAdamW.state_dict()")
+        bank.assert_whole(f"{type(self).__name__}.state_dict()")
         if self.deferred_pending:
-            raise RuntimeError("FusedAdamW.state_dict(): an update deferred to the next step is pending -- flush it first "
+            raise RuntimeError(f"{type(self).__name__}.state_dict(): an update deferred to the next step is pending -- flush it first "
                                "(launch(groups=..., reuse_norm=True); deferred_pending = False)")
         state = {}
         for name, p in bank._trainable:
             off = bank.offset[id(p)]
-            state[name] = dict(step=self.step_count, exp_avg=bank._view(bank.exp_avg, off, p).detach().clone().contiguous(),
-                               exp_avg_sq=bank._view(bank.exp_avg_sq, off, p).detach().clone().contiguous())
+            state[name] = {"step": self.step_count, "exp_avg": bank._view(bank.exp_avg, off, p).detach().clone().contiguous(),
+                           self.second_key: bank._view(bank.exp_avg_sq, off, p).detach().clone().contiguous()}
         groups = [dict(lr=pg["lr"], weight_decay=pg["weight_decay"], betas=self.betas, eps=self.eps) for pg in self.param_groups]
-        return dict(state=state, param_groups=groups, step=self.step_count)
+        return dict(state=state, param_groups=groups, step=self.step_count, algo=self.algo)
 
     @torch.no_grad()
     def load_state_dict(self, sd: dict):
+        """A state dict without "algo" is AdamW's (files written before the key existed)."""
         bank = self.bank
+        theirs = sd.get("algo", "adamw")
+        if theirs != self.algo:
+            raise ValueError(f"optimizer state was written by {theirs!r}; {type(self).__name__} ({self.algo!r}) cannot continue from it")
         missing = [n for n, _p in bank._trainable if n not in sd["state"]]
         if missing:
             raise KeyError(f"optimizer state lacks {len(missing)} parameters, e.g. {missing[:3]}")
@@ -217,7 +231,21 @@ class FusedAdamW:
             off = bank.offset[id(p)]
             st = sd["state"][name]
             bank._view(bank.exp_avg, off, p).copy_(st["exp_avg"].to(bank.device, torch.float32))
-            bank._view(bank.exp_avg_sq, off, p).copy_(st["exp_avg_sq"].to(bank.device, torch.float32))
+            bank._view(bank.exp_avg_sq, off, p).copy_(st[self.second_key].to(bank.device, torch.float32))
         self.step_count = int(sd.get("step", 0))
         for pg, src in zip(self.param_groups, sd.get("param_groups", [])):
             pg["lr"], pg["weight_decay"] = src["lr"], src["weight_decay"]
+
+
+class FusedAdam(FusedAdamW):
+    """torch.optim.Adam(groups, lr=..., betas=...) of setup_e2e_optimizer (src/optimization/utils.py:118-119, 126-127): no amsgrad, eps 1e-8,
+    weight decay added to the gradient.  Same construction, step / launch modes and checkpoint layout as FusedAdamW."""
+    algo, algo_code, second_key, default_eps = "adam", OPT_ADAM, "exp_avg_sq", 1e-8
+
+    def _update(self, p, g, m, v2, w16, hp, sq):
+        ops.optim_step(self.algo_code, p, g, m, v2, w16, hp, sq)
+
+
+class FusedAdamax(FusedAdam):
+    """torch.optim.Adamax (src/optimization/utils.py:120-121): the infinity-norm state ("exp_inf") lives in the bank's exp_avg_sq buffer."""
+    algo, algo_code, second_key, default_eps = "adamax", OPT_ADAMAX, "exp_inf", 1e-8

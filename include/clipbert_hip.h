@@ -421,6 +421,20 @@ int cb_sq_sum_det_bf16(const void* g16, int64_t n, float* out_accum, float* ws, 
 int cb_adamw_g16(float* p, const void* g16, float* m, float* v, void* w16, int64_t n, const float* hyper, const float* grad_sq_sum,
                  void* stream);
 
+/* The three optimizers of setup_e2e_optimizer (src/optimization/utils.py:96-128: cfg.optim = "adamw" | "adam" | "adamax") behind one
+ * entry point, each as one fused pass over a flat range with the clip, grad_scale, skip flag, bf16 weight refresh and `hyper` array of
+ * cb_adamw (CB_HP_EPS is whatever the caller packs: torch's default 1e-8 for the two below, the reference passes none):
+ *   CB_OPT_ADAMW   src/optimization/adamw.py:40-103 -- dispatches to cb_adamw / cb_adamw_g16, bit-identical to them;
+ *   CB_OPT_ADAM    torch.optim.Adam without amsgrad (utils.py:118-119, 126-127): g += wd p (L2 decay on the gradient, when wd != 0);
+ *                  m = b1 m + (1 - b1) g;  v2 = b2 v2 + (1 - b2) g^2;  p -= (lr / bc1) m / (sqrt(v2) / sqrt(bc2) + eps);
+ *   CB_OPT_ADAMAX  torch.optim.Adamax (utils.py:120-121, 126-127): the same g and m;  v2 = max(b2 v2, |g| + eps) (torch's exp_inf);
+ *                  p -= (lr / bc1) m / v2;  CB_HP_BC2 is ignored.
+ * grad_dtype: CB_F32 or CB_BF16, the type of g (the reduced data-parallel wire image is bf16).  An unknown algo or grad_dtype and a
+ * null p / g / m / v2 / hyper fail with a message and launch nothing. */
+enum { CB_OPT_ADAMW = 0, CB_OPT_ADAM = 1, CB_OPT_ADAMAX = 2 };
+int cb_optim_step(int32_t algo, int32_t grad_dtype, float* p, const void* g, float* m, float* v2, void* w16, int64_t n, const float* hyper,
+                  const float* grad_sq_sum, void* stream);
+
 /* ELU followed by BatchNorm1d over the batch dimension -- regressor[1:3] of ClipBertForRegression
  * (src/modeling/modeling.py:461-466; torch.nn.ELU + torch.nn.BatchNorm1d semantics).  x, y: (B, D).  training = 1: batch
  * statistics (biased variance), running_mean / running_var updated in place with `momentum` (unbiased variance); training = 0:
@@ -442,7 +456,8 @@ const char* cb_last_error(void);
  *     new size are unaffected), accumulate = 2 (first writer), cb_sq_sum_fold;
  * 7 = cb_gemm_desc.tile = 9 (few rows), chosen by itself for M <= 64: the same result up to the order of the fp32 additions;
  *     cb_gemm_group takes strided batches / a_rowsum on the unsplit bf16 weight-gradient form; cb_stem_pool_u8; cb_zero_ranges;
- * 8 = cb_resize_pack_u8 (raw-frame ingest: resize + pad + ImageNorm of native-resolution uint8 frames; nothing else changed) */
+ * 8 = cb_resize_pack_u8 (raw-frame ingest: resize + pad + ImageNorm of native-resolution uint8 frames; nothing else changed);
+ * 9 = cb_optim_step (CB_OPT_ADAM / CB_OPT_ADAMAX beside AdamW: the reference's other two cfg.optim choices; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
