@@ -12,6 +12,9 @@ materialised per batch).  Here
   per-frame ``ImageResize`` (bilinear, longer side -> max_img_size) + ``ImagePad`` (src/datasets/dataset_base.py:270-273,
   src/datasets/data_utils.py:112-253) run on the GPU inside ``cb_resize_pack_u8``, which writes the stem's packed image
   directly.  No fp32 frame is ever built on the host;
+* ... and for the decoder's own **YUV 4:2:0 planes** (``collate_yuv_frames``: I420 from software decoders, NV12 from hardware
+  ones): the same ``RawFrames`` with ``pixfmt`` / ``matrix`` set, 1.5 bytes per pixel instead of 3, no colour conversion in the
+  loader workers -- ``cb_resize_pack_yuv420`` converts each bilinear tap in the same launch;
 * host staging is **pinned and double-buffered**: two pinned slots per tensor key, batch i+1 is copied host->pinned->HBM on a
   side HIP stream while batch i computes; a slot is reused only after the event recorded behind its last H2D copy has
   completed, and the consumer stream waits on the copy's event (not on the whole side stream);
@@ -50,20 +53,33 @@ class RawFrames:
     it stands for: ``view`` / ``reshape`` / ``transpose`` / indexing / ``contiguous`` act on them exactly as they would on that
     tensor, by permuting and slicing the TABLE ROWS only -- pixel bytes are never copied on the host, and frames a slice leaves
     out simply are not referenced any more -- and still travel: ``to`` / ``PrefetchLoader`` upload the WHOLE ``flat`` buffer of a
-    sliced RawFrames (slice on the device, after the copy; re-collate on the host to ship less).  The model consumes it wherever it takes a frame tensor (modeling.cnn_forward)."""
+    sliced RawFrames (slice on the device, after the copy; re-collate on the host to ship less).  The model consumes it wherever it takes a frame tensor (modeling.cnn_forward).
+
+    ``pixfmt``: "rgb" (the above) or "i420" / "nv12" -- every frame is then its tightly packed YUV 4:2:0 planes (Y h x w, then U and V
+    of ceil(h / 2) x ceil(w / 2) each, or the two interleaved; ``hwc`` is ignored) and ``matrix`` ("bt601": limited range, what
+    libswscale applies to an untagged stream; "bt601-full", "bt709", "bt709-full") is the conversion it stands for: the RGB frames
+    tests/yuv_restatement.py spells out, nearest chroma, rounded to uint8 before the resize."""
+    PIXFMTS = ("rgb", "i420", "nv12")
+    MATRICES = ("bt601", "bt601-full", "bt709", "bt709-full")
 
     def __init__(self, flat: torch.Tensor, table: torch.Tensor, max_img_size: int, hwc: bool = True,
-                 host_table: Optional[torch.Tensor] = None):
+                 host_table: Optional[torch.Tensor] = None, pixfmt: str = "rgb", matrix: str = "bt601"):
         assert flat.dtype == torch.uint8 and flat.dim() == 1
         assert table.dtype == torch.int64 and table.dim() >= 1 and table.shape[-1] == 5
         if host_table is None and not table.is_cuda:
             host_table = table
         assert host_table is None or (not host_table.is_cuda and host_table.shape == table.shape)
         self.flat, self.table, self.host_table = flat, table, host_table
+        assert pixfmt in self.PIXFMTS and matrix in self.MATRICES, (pixfmt, matrix)
         self.max_img_size, self.hwc = int(max_img_size), bool(hwc)
+        self.pixfmt, self.matrix = pixfmt, matrix
+
+    def _with(self, flat, table, host_table):
+        """the same kind of frames (size, layout, pixel format, matrix) over other tensors"""
+        return RawFrames(flat, table, self.max_img_size, self.hwc, host_table, self.pixfmt, self.matrix)
 
     def _like(self, table, host_table):
-        return RawFrames(self.flat, table, self.max_img_size, self.hwc, host_table)
+        return self._with(self.flat, table, host_table)
 
     def _both(self, fn):
         """the same table-row operation on the device table and its host copy"""
@@ -133,8 +149,7 @@ class RawFrames:
     def to(self, device, non_blocking: bool = False):
         device = torch.device(device)
         host = self.host_table if self.host_table is not None else (self.table if not self.table.is_cuda else None)
-        return RawFrames(self.flat.to(device, non_blocking=non_blocking), self.table.to(device, non_blocking=non_blocking),
-                         self.max_img_size, self.hwc, host)
+        return self._with(self.flat.to(device, non_blocking=non_blocking), self.table.to(device, non_blocking=non_blocking), host)
 
     def packed_table(self):
         """(table, host_table) as contiguous (n_frames, 5) row lists in the order of the leading dimensions (what the kernel reads)"""
@@ -144,7 +159,19 @@ class RawFrames:
         return t, (t if self.host_table is self.table else self.host_table.reshape(-1, 5).contiguous())
 
     def __repr__(self):
-        return f"RawFrames(shape={tuple(self.shape)}, bytes={self.flat.numel()}, hwc={self.hwc}, device={self.device})"
+        kind = f"hwc={self.hwc}" if self.pixfmt == "rgb" else f"pixfmt={self.pixfmt}, matrix={self.matrix}"
+        return f"RawFrames(shape={tuple(self.shape)}, bytes={self.flat.numel()}, {kind}, device={self.device})"
+
+
+def _frame_rows(rows, off: int, t: int, h: int, w: int, frame_bytes: int, max_img_size: int) -> int:
+    """append the table rows of one video's ``t`` frames of h x w, ``frame_bytes`` each, starting at byte ``off`` -> the next offset"""
+    nh, nw = resize_size(h, w, max_img_size)
+    if min(h, w, nh, nw) < 1:
+        raise ValueError(f"a {h} x {w} frame resizes to {nh} x {nw} at max_img_size {max_img_size} (is_extreme_aspect_ratio videos are skipped by the dataset)")
+    for _ in range(t):
+        rows.append([off, h, w, nh, nw])
+        off += frame_bytes
+    return off
 
 
 def collate_raw_frames(videos: Sequence[torch.Tensor], max_img_size: int, hwc: bool = True) -> RawFrames:
@@ -158,15 +185,33 @@ def collate_raw_frames(videos: Sequence[torch.Tensor], max_img_size: int, hwc: b
         assert v.dtype == torch.uint8 and v.dim() == 4 and v.shape[0] == t0, "every video contributes the same number of uint8 frames"
         assert v.shape[3 if hwc else 1] == 3, f"expected {'(T, h, w, 3)' if hwc else '(T, 3, h, w)'} frames, got {tuple(v.shape)}"
         h, w = (v.shape[1], v.shape[2]) if hwc else (v.shape[2], v.shape[3])
-        nh, nw = resize_size(h, w, max_img_size)
-        if min(h, w, nh, nw) < 1:
-            raise ValueError(f"a {h} x {w} frame resizes to {nh} x {nw} at max_img_size {max_img_size} (is_extreme_aspect_ratio videos are skipped by the dataset)")
-        for _ in range(t0):
-            rows.append([off, h, w, nh, nw])
-            off += 3 * h * w
+        off = _frame_rows(rows, off, t0, h, w, 3 * h * w, max_img_size)
         chunks.append(v.contiguous().view(-1))
     table = torch.tensor(rows, dtype=torch.int64).view(len(videos), t0, 5)
     return RawFrames(torch.cat(chunks), table, max_img_size, hwc)
+
+
+def yuv420_frame_bytes(h: int, w: int) -> int:
+    """bytes of one tightly packed YUV 4:2:0 frame (I420 and NV12 alike): the luma plane and two chroma planes of half the size, rounded up"""
+    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+
+
+def collate_yuv_frames(videos: Sequence, max_img_size: int, layout: str = "i420", matrix: str = "bt601") -> RawFrames:
+    """collate_raw_frames for the decoder's YUV 4:2:0 planes: ``videos`` holds one ``(frames_u8, h, w)`` per video, ``frames_u8`` a
+    (T, yuv420_frame_bytes(h, w)) uint8 tensor whose rows are the frames' planes -- ``layout`` "i420": Y, U, V (for even sizes PyAV's
+    ``frame.to_ndarray(format="yuv420p")`` flattened); "nv12": Y, then interleaved UV -- the same T everywhere, any h x w per video.
+    ``matrix``: the conversion the stream asks for (RawFrames).  One concatenation of the bytes; nothing is converted or resized here."""
+    assert len(videos) > 0 and layout in ("i420", "nv12") and matrix in RawFrames.MATRICES, (layout, matrix)
+    t0 = videos[0][0].shape[0]
+    rows, chunks, off = [], [], 0
+    for v, h, w in videos:
+        h, w = int(h), int(w)
+        assert v.dtype == torch.uint8 and v.dim() == 2 and v.shape[0] == t0, "every video contributes the same number of uint8 frames"
+        assert v.shape[1] == yuv420_frame_bytes(h, w), f"a {h} x {w} 4:2:0 frame has {yuv420_frame_bytes(h, w)} bytes, got {v.shape[1]}"
+        off = _frame_rows(rows, off, t0, h, w, v.shape[1], max_img_size)
+        chunks.append(v.contiguous().view(-1))
+    table = torch.tensor(rows, dtype=torch.int64).view(len(videos), t0, 5)
+    return RawFrames(torch.cat(chunks), table, max_img_size, pixfmt=layout, matrix=matrix)
 
 
 class InfiniteIterator:
@@ -227,8 +272,8 @@ class PrefetchLoader:
         if isinstance(obj, RawFrames):                  # flat bytes and table: two keys of the pinned double buffer
             table = obj.table.contiguous()
             host = obj.host_table if obj.host_table is not None else (table if not table.is_cuda else None)
-            return RawFrames(self._move(obj.flat, slot, f"{prefix}/flat"), self._move(table, slot, f"{prefix}/table"),
-                             obj.max_img_size, obj.hwc, host.contiguous() if host is not None else None)
+            return obj._with(self._move(obj.flat, slot, f"{prefix}/flat"), self._move(table, slot, f"{prefix}/table"),
+                             host.contiguous() if host is not None else None)
         if torch.is_tensor(obj):
             return self._stage(prefix, slot, obj) if obj.device.type == "cpu" else obj.to(self.device, non_blocking=True)
         if isinstance(obj, dict):

@@ -245,6 +245,25 @@ def resize_pack_u8(flat_u8: torch.Tensor, table: torch.Tensor, n: int, size: int
     return dst
 
 
+def resize_pack_yuv420(flat_u8: torch.Tensor, table: torch.Tensor, n: int, size: int, dtype: torch.dtype, mean, std, layout: str = "i420",
+                       matrix: str = "bt601", pad: int = 3, extra_w: int = 0, host_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cb_resize_pack_yuv420: resize_pack_u8 for ``n`` YUV 4:2:0 frames lying back to back in ``flat_u8`` as their tightly packed
+    planes -- ``layout`` "i420" (Y, U, V) or "nv12" (Y, interleaved UV), h * w + 2 * ceil(h / 2) * ceil(w / 2) bytes each -- converted
+    with ``matrix`` ("bt601", "bt601-full", "bt709", "bt709-full"; nearest chroma) tap by tap.  Bit-equal to resize_pack_u8(hwc=False)
+    on the converted uint8 RGB frames.  ``table`` / ``host_table`` as there.  One launch, no host sync."""
+    assert flat_u8.dtype == torch.uint8 and flat_u8.dim() == 1 and flat_u8.is_contiguous()
+    assert table.dtype == torch.int64 and tuple(table.shape) == (n, 5) and table.is_contiguous() and table.device == flat_u8.device
+    if host_table is not None:
+        assert host_table.dtype == torch.int64 and tuple(host_table.shape) == (n, 5) and host_table.is_contiguous() and not host_table.is_cuda
+    hp, wp = size + 2 * pad, size + 2 * pad + extra_w
+    dst = torch.empty(n, hp, wp, 4, dtype=dtype, device=flat_u8.device)
+    _chk(_lib.get().cb_resize_pack_yuv420(dtype_code(dtype), _ptr(flat_u8), flat_u8.numel(), _ptr(table),
+                                          host_table.data_ptr() if host_table is not None else None, n, _lib.YUV_LAYOUTS[layout],
+                                          _lib.YUV_MATRICES[matrix], _f3(mean), _f3(std), _ptr(dst), size, hp, wp, pad, _stream(flat_u8)),
+         "cb_resize_pack_yuv420")
+    return dst
+
+
 def image_norm(frames_u8: torch.Tensor, mean, std) -> torch.Tensor:
     """ImageNorm (a1): uint8 (..., 3, H, W) -> fp32."""
     assert frames_u8.dtype == torch.uint8 and frames_u8.is_contiguous() and frames_u8.shape[-3] == 3

@@ -219,6 +219,29 @@ int cb_resize_pack_u8(int32_t dtype, const uint8_t* flat, int64_t flat_bytes, co
                       int32_t hwc, const float* mean3, const float* std3, void* dst, int32_t S, int32_t Hp, int32_t Wp, int32_t pad,
                       void* stream);
 
+/* The same ingest from the planes of a YUV 4:2:0 frame, as decoders emit them (software decoders: planar I420; hardware decoders: NV12):
+ * no colour conversion on the host, 1.5 bytes per pixel instead of 3 across PCIe.  Every argument that cb_resize_pack_u8 has means what
+ * it means there (dst, table and its five columns, table_host, mean3 / std3, N <= 65535, no host synchronisation, a row that does not
+ * fit the buffer -> an all-padding frame).  A frame lies tightly packed at byte_offset, ch = (h + 1) / 2, cw = (w + 1) / 2 (odd sizes
+ * are legal; row pitches are not supported), h * w + 2 * ch * cw bytes:
+ *   layout = CB_YUV_I420 : Y (h x w), then U (ch x cw), then V (ch x cw)
+ *   layout = CB_YUV_NV12 : Y (h x w), then interleaved UV (ch x 2 cw)
+ * DEFINITION: the result equals, bit for bit, what cb_resize_pack_u8(hwc = 0) writes for the uint8 RGB frame in which pixel (i, j) is
+ * the conversion of Y(i, j) with the chroma sample (i >> 1, j >> 1) (nearest replication: what libswscale's unscaled yuv420p -> rgb24
+ * path does) -- each of the four bilinear taps is converted to RGB BYTES first (round to nearest even, clamp to 0..255), then blended.
+ * With cb = U - 128, cr = V - 128, in fp32, every multiply and add rounded on its own, in this order:
+ *   matrix                      y'                 R                  G                                B
+ *   CB_YUV_BT601      limited   1.164383 (Y - 16)  y' + 1.596027 cr   y' - 0.391762 cb - 0.812968 cr   y' + 2.017232 cb
+ *   CB_YUV_BT601_FULL (JPEG)    Y                  y' + 1.402 cr      y' - 0.344136 cb - 0.714136 cr   y' + 1.772 cb
+ *   CB_YUV_BT709      limited   1.164383 (Y - 16)  y' + 1.792741 cr   y' - 0.213249 cb - 0.532909 cr   y' + 2.112402 cb
+ *   CB_YUV_BT709_FULL           Y                  y' + 1.5748 cr     y' - 0.187324 cb - 0.468124 cr   y' + 1.8556 cb
+ * (BT.601 limited is what libswscale applies to an untagged stream.) */
+enum { CB_YUV_I420 = 0, CB_YUV_NV12 = 1 };
+enum { CB_YUV_BT601 = 0, CB_YUV_BT601_FULL = 1, CB_YUV_BT709 = 2, CB_YUV_BT709_FULL = 3 };
+int cb_resize_pack_yuv420(int32_t dtype, const uint8_t* flat, int64_t flat_bytes, const int64_t* table, const int64_t* table_host, int32_t N,
+                          int32_t layout, int32_t matrix, const float* mean3, const float* std3, void* dst, int32_t S, int32_t Hp, int32_t Wp,
+                          int32_t pad, void* stream);
+
 /* ImageNorm alone (a1): uint8 (n) -> fp32 (x - mean[c]) / std[c], NCHW with plane size hw.
  * mean3 / std3: HOST arrays of 3 floats. */
 int cb_image_norm(const uint8_t* src, float* dst, const float* mean3, const float* std3,
@@ -457,7 +480,8 @@ const char* cb_last_error(void);
  * 7 = cb_gemm_desc.tile = 9 (few rows), chosen by itself for M <= 64: the same result up to the order of the fp32 additions;
  *     cb_gemm_group takes strided batches / a_rowsum on the unsplit bf16 weight-gradient form; cb_stem_pool_u8; cb_zero_ranges;
  * 8 = cb_resize_pack_u8 (raw-frame ingest: resize + pad + ImageNorm of native-resolution uint8 frames; nothing else changed);
- * 9 = cb_optim_step (CB_OPT_ADAM / CB_OPT_ADAMAX beside AdamW: the reference's other two cfg.optim choices; nothing else changed) */
+ * 9 = cb_optim_step (CB_OPT_ADAM / CB_OPT_ADAMAX beside AdamW: the reference's other two cfg.optim choices; nothing else changed);
+ * 10 = cb_resize_pack_yuv420 (the raw-frame ingest from I420 / NV12 planes; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
