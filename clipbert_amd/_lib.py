@@ -89,6 +89,9 @@ _SIGNATURES = {
     "cb_attention_fwd": [i32, vp, vp, vp, vp, i32, i32, i32, f32, u64, vp, vp],
     "cb_attention_bwd": [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, u64, vp, vp],
     "cb_cross_entropy": [vp, i64, vp, vp, vp, vp, i64, i32, i64, vp],
+    "cb_mlm_select": [vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "cb_mlm_loss_fwd": [vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp],
+    "cb_mlm_loss_bwd": [i32, vp, i64, vp, vp, vp, i64, vp, vp, i64, i32, i32, vp],
     "cb_colsum": [i32, vp, i64, vp, i64, i32, vp],
     "cb_cast": [i32, vp, i32, vp, i64, vp],
     "cb_act_bwd": [i32, i32, vp, vp, vp, i64, vp],

@@ -5,7 +5,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..ops import ACT_GELU, ACT_NONE, ACT_RELU, KROW
+from ..ops import ACT_GELU, ACT_NONE, ACT_RELU, KROW, KROW_GATHER, ROWK_GATHER
 from .cnn import conv_gather
 from .encoder import ClipBertBaseModel, _drop_p, _linear_wgrad
 from .modules import BatchNorm1d, Linear, _cfg_get, _make_mlp, _PreTrainingHeads, as_config
@@ -18,15 +18,28 @@ def _row_gather(rt, operand, rows, k, device):
     return conv_gather(rt, operand, nseg, 1, seglen, k, 1, 1, 0, device, sN=segstride * k, sH=0)
 
 
+def _slot_gather(operand, sel, k):
+    """the same block for the ``sel.cap`` rows of a (*, k) matrix that cb_mlm_select picked on the device: its table instead of a host-built one"""
+    kw = dict(R=1, S=1, Cin=k, H=1, W=sel.lt, sH=0, sW=k)
+    kw.update(dict(a_mode=ROWK_GATHER, a_tab=sel.tab, lda=0) if operand == "a" else dict(b_mode=KROW_GATHER, b_tab=sel.tab, ldb=0))
+    return kw
+
+
+def _gather(rt, operand, rows, k, device):
+    return _slot_gather(operand, rows, k) if isinstance(rows, ops.MlmSelection) else _row_gather(rt, operand, rows, k, device)
+
+
 class _LinearFn(torch.autograd.Function):
-    """y = act(x W^T + b).  ``rows`` = (n_seg, seg_len, seg_stride_rows) selects x rows (b*stride + t)."""
+    """y = act(x W^T + b).  ``rows`` = (n_seg, seg_len, seg_stride_rows) selects x rows (b*stride + t); an ops.MlmSelection selects the
+    rows its device-built table names (padding slots read zeros; their gradient rows land in a dump row that is cut off)."""
     @staticmethod
     def forward(ctx, anchor, x, rt, weight, bias, act, out_f32, rows):
         n, k = weight.shape
         dev = x.device
         x2 = x.reshape(-1, k)
-        m = x2.shape[0] if rows is None else rows[0] * rows[1]
-        gather = {} if rows is None else _row_gather(rt, "a", rows, k, dev)
+        slots = isinstance(rows, ops.MlmSelection)
+        m = x2.shape[0] if rows is None else rows.cap if slots else rows[0] * rows[1]
+        gather = {} if rows is None else _gather(rt, "a", rows, k, dev)
         out_dt = torch.float32 if out_f32 else rt.dtype
         ld = n if n < 4 else (n + 3) // 4 * 4              # (1- / 2-column head outputs stay contiguous: the losses read them in place)
         store = torch.empty(m, ld, dtype=out_dt, device=dev)
@@ -53,15 +66,17 @@ class _LinearFn(torch.autograd.Function):
             g = ops.act_bwd(act, g.contiguous(), ctx.y.contiguous().to(dt))
         x2, rows = ctx.x2, ctx.rows
         gb = _linear_wgrad(g, x2, m, n, k, bank.grad_image(weight), bank.grad_image(bias) if bias is not None else None,
-                           gather=None if rows is None else _row_gather(rt, "b", rows, k, dy.device), defer_bias=True)
+                           gather=None if rows is None else _gather(rt, "b", rows, k, dy.device), defer_bias=True)
         if rows is None:
             dx, rowmap = torch.empty(x2.shape, dtype=dt, device=dy.device), None
+        elif isinstance(rows, ops.MlmSelection):        # (one dump row behind the real ones takes the padding slots' zeros)
+            dx, rowmap = ops.zeros((x2.shape[0] + 1, k), dt, dy.device), rows.rowmap
         else:                                           # (rows outside the segments get no gradient)
             dx, rowmap = ops.zeros(x2.shape, dt, dy.device), rt.strided_rowmap(rows[0], 1, rows[2], 1, rows[1], 1, dy.device)
         ops.gemm(g, bank.compute(weight), m, k, n, out=dx, lda=g.stride(0), b_mode=KROW, c_rowmap=rowmap)
         if gb is not None:
             ops.colsum(g, gb, m, n)
-        return None, dx.view(ctx.x_shape), None, None, None, None, None, None
+        return None, dx[:x2.shape[0]].view(ctx.x_shape), None, None, None, None, None, None
 
 
 class _LayerNormFn(torch.autograd.Function):
@@ -95,6 +110,37 @@ class _CrossEntropyFn(torch.autograd.Function):
         logits, labels = ctx.saved_tensors
         _, dlogits = ops.cross_entropy(logits, labels, want_loss=False, dloss=dloss.contiguous(), want_grad=True)
         return dlogits, None
+
+
+class _MlmDecoderLossFn(torch.autograd.Function):
+    """Tied decoder (transformers.py:504-515) + masked-LM loss and arg-max (modeling.py:287-298, run_pretrain.py:229-237) on the ``sel.cap``
+    compact rows: fp32 logits (cap, V) -> per-row loss (B * Lt,), zeros at unlabelled rows; the arg-max lands in sel.pred_rows.  ONE node
+    for the two stages: autograd converts a gradient to the dtype of the tensor it belongs to, so fp32 logits handed from a decoder node
+    to a loss node would bring back the fp32 gradient matrix and the cast that cb_mlm_loss_bwd exists to avoid."""
+    @staticmethod
+    def forward(ctx, anchor, h, rt, weight, bias, sel):
+        n, k = weight.shape
+        m = sel.cap
+        logits = torch.empty(m, (n + 3) // 4 * 4, dtype=torch.float32, device=h.device)[:, :n]
+        ops.gemm(h, rt.bank.compute(weight), m, n, k, out=logits, shift=bias, act=ACT_NONE)
+        lse = ops.mlm_loss_fwd(logits, sel)
+        ctx.rt, ctx.weight, ctx.bias, ctx.sel, ctx.saved = rt, weight, bias, sel, (h, logits, lse)
+        return sel.loss_rows
+
+    @staticmethod
+    def backward(ctx, dloss):
+        rt, weight, bias, sel = ctx.rt, ctx.weight, ctx.bias, ctx.sel
+        h, logits, lse = ctx.saved
+        bank = rt.bank
+        n, k = weight.shape
+        m = sel.cap
+        g = ops.mlm_loss_bwd(logits, lse, sel, dloss.contiguous(), rt.dtype)
+        gb = _linear_wgrad(g, h, m, n, k, bank.grad_image(weight), bank.grad_image(bias), defer_bias=True)
+        dh = torch.empty(h.shape, dtype=rt.dtype, device=h.device)
+        ops.gemm(g, bank.compute(weight), m, k, n, out=dh, lda=g.stride(0), b_mode=KROW)
+        if gb is not None:
+            ops.colsum(g, gb, m, n)
+        return None, dh, None, None, None, None
 
 
 class _HeadLossFn(torch.autograd.Function):
@@ -267,24 +313,54 @@ class ClipBertForPreTraining(_ClipBertHead):
     def __init__(self, config):
         super().__init__(config)
         self.cls = _PreTrainingHeads(self.config, self.bert.embeddings.word_embeddings.weight)
+        self.mlm_counts: Optional[torch.Tensor] = None    # device [count, dropped] of the labelled-rows mode (forward)
 
     def get_output_embeddings(self):
         return self.cls.predictions.decoder
 
-    def forward(self, text_input_ids, visual_inputs, text_input_mask, mlm_labels=None, itm_labels=None, src_row=None):
+    def labelled_mlm_head(self, seq, lt, mlm_labels, mlm_capacity=None):
+        """The masked-LM head on the labelled text rows of the (B, L, d) encoder output only: cb_mlm_select -> transform dense + GELU on the
+        gathered rows -> LayerNorm -> tied decoder -> loss + arg-max, every matrix ``cap`` rows tall.  -> (loss (B * Lt,), pred (B, Lt))"""
+        rt, pred = self.rt, self.cls.predictions
+        b, L, d = seq.shape
+        cap = (max(1, b * lt if mlm_capacity is None else int(mlm_capacity)) + 63) // 64 * 64
+        if self.mlm_counts is None or self.mlm_counts.device != seq.device:
+            self.mlm_counts = ops.zeros(2, torch.int64, seq.device)
+        sel = ops.mlm_select(mlm_labels.reshape(-1).contiguous(), lt, L, d, self.config.vocab_size, cap, counts=self.mlm_counts)
+        h = _LinearFn.apply(rt.anchor, seq, rt, pred.transform.dense.weight, pred.transform.dense.bias, ACT_GELU, False, sel)
+        h = _LayerNormFn.apply(rt.anchor, h, rt, pred.transform.LayerNorm)
+        loss = _MlmDecoderLossFn.apply(rt.anchor, h, rt, pred.decoder.weight, pred.bias, sel)
+        return loss, sel.pred_rows.view(b, lt)
+
+    def forward(self, text_input_ids, visual_inputs, text_input_mask, mlm_labels=None, itm_labels=None, src_row=None, mlm_rows="all",
+                mlm_capacity=None):
+        """``mlm_rows`` = "labelled": the masked-LM head runs on the labelled text rows only (cb_mlm_select compacts them on the device
+        into ``mlm_capacity`` slots, rounded up to 64; None = every text row fits): ``mlm_scores`` is None, ``mlm_loss`` is the same
+        (B * Lt,) vector, and ``mlm_pred`` (B, Lt) holds the arg-max at labelled positions, -100 elsewhere.  self.mlm_counts (device
+        int64: [labelled rows of the last call, rows dropped so far for want of slots]) tells a caller whether a fixed capacity held."""
+        if mlm_rows not in ("all", "labelled"):
+            raise ValueError(f"mlm_rows must be 'all' or 'labelled', not {mlm_rows!r}")
+        if mlm_rows == "labelled" and mlm_labels is None:
+            raise ValueError("mlm_rows='labelled' needs mlm_labels")
         rt = self.rt
         seq, pooled = self.bert(text_input_ids, visual_inputs, text_input_mask, src_row)
         b, L, d = seq.shape
         lt = text_input_mask.shape[1]
         pred = self.cls.predictions
+        rel = self.cls.seq_relationship
+        v = self.config.vocab_size
+        if mlm_rows == "labelled":
+            mlm_loss, mlm_pred = self.labelled_mlm_head(seq, lt, mlm_labels, mlm_capacity)
+            itm = _LinearFn.apply(rt.anchor, pooled, rt, rel.weight, rel.bias, ACT_NONE, True, None)
+            itm_loss = cross_entropy_none(itm.view(-1, 2), itm_labels.view(-1)) if itm_labels is not None else 0
+            return dict(mlm_scores=None, mlm_loss=mlm_loss, mlm_labels=mlm_labels, itm_scores=itm, itm_loss=itm_loss,
+                        itm_labels=itm_labels, mlm_pred=mlm_pred)
         # heads on the TEXT rows only (modeling.py:283-285): gathered inside the GEMM loader
         h = _LinearFn.apply(rt.anchor, seq, rt, pred.transform.dense.weight, pred.transform.dense.bias, ACT_GELU, False,
                             (b, lt, L))
         h = _LayerNormFn.apply(rt.anchor, h, rt, pred.transform.LayerNorm)
         scores = _LinearFn.apply(rt.anchor, h, rt, pred.decoder.weight, pred.bias, ACT_NONE, True, None)
-        rel = self.cls.seq_relationship
         itm = _LinearFn.apply(rt.anchor, pooled, rt, rel.weight, rel.bias, ACT_NONE, True, None)
-        v = self.config.vocab_size
         mlm_loss = cross_entropy_none(scores, mlm_labels.view(-1)) if mlm_labels is not None else 0
         itm_loss = cross_entropy_none(itm.view(-1, 2), itm_labels.view(-1)) if itm_labels is not None else 0
         return dict(mlm_scores=scores.view(b, lt, v), mlm_loss=mlm_loss, mlm_labels=mlm_labels, itm_scores=itm,

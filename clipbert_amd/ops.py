@@ -516,6 +516,57 @@ def cross_entropy(logits, labels, want_loss=True, dloss=None, want_grad=False, i
     return loss, dlogits
 
 
+class MlmSelection:
+    """What cb_mlm_select leaves on the device for one batch: the labelled text rows compacted into ``cap`` slots (see the header)."""
+    __slots__ = ("cap", "rows", "lt", "l", "d", "v", "ignore_index", "slot_row", "slot_label", "tab", "rowmap", "counts", "loss_rows", "pred_rows")
+
+
+def mlm_select(labels: torch.Tensor, lt: int, l: int, d: int, v: int, cap: int, counts: Optional[torch.Tensor] = None,
+               ignore_index: int = -100) -> MlmSelection:
+    """cb_mlm_select: labels int64 (B * Lt,) -> MlmSelection.  ``counts``: int64 (2,) = [count, dropped so far]; a new zeroed one when None
+    (pass the same tensor again to keep the tally of drops).  One launch, no host sync."""
+    assert labels.dtype == torch.int64 and labels.dim() == 1 and labels.is_contiguous()
+    rows, dev = labels.numel(), labels.device
+    s = MlmSelection()
+    s.cap, s.rows, s.lt, s.l, s.d, s.v, s.ignore_index = cap, rows, lt, l, d, v, ignore_index
+    s.slot_row = torch.empty(cap, dtype=torch.int32, device=dev)
+    s.slot_label = torch.empty(cap, dtype=torch.int64, device=dev)
+    s.tab = torch.empty(cap, dtype=torch.int64, device=dev)                    # cb_pixel entries
+    s.rowmap = torch.empty(cap, dtype=torch.int32, device=dev)
+    s.counts = counts if counts is not None else zeros(2, torch.int64, dev)
+    assert s.counts.dtype == torch.int64 and s.counts.numel() == 2 and s.counts.is_contiguous()
+    s.loss_rows = torch.empty(rows, dtype=torch.float32, device=dev)
+    s.pred_rows = torch.empty(rows, dtype=torch.int64, device=dev)
+    _chk(_lib.get().cb_mlm_select(_ptr(labels), ignore_index, rows, lt, l, d, v, cap, _ptr(s.slot_row), _ptr(s.slot_label), _ptr(s.tab),
+                                  _ptr(s.rowmap), _ptr(s.counts), _ptr(s.loss_rows), _ptr(s.pred_rows), _stream(labels)), "cb_mlm_select")
+    return s
+
+
+def mlm_loss_fwd(logits: torch.Tensor, sel: MlmSelection) -> torch.Tensor:
+    """cb_mlm_loss_fwd on the compact fp32 logits (cap, V) (row stride may exceed V): scatters the loss and the arg-max of every
+    labelled slot into sel.loss_rows / sel.pred_rows and returns lse (cap,) for the backward (undefined at padding slots)."""
+    cap, v = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and cap == sel.cap and v == sel.v
+    lse = torch.empty(cap, dtype=torch.float32, device=logits.device)
+    _chk(_lib.get().cb_mlm_loss_fwd(_ptr(logits), logits.stride(0), _ptr(sel.slot_row), _ptr(sel.slot_label), sel.ignore_index, cap, v,
+                                    _ptr(lse), _ptr(sel.loss_rows), _ptr(sel.pred_rows), _stream(logits)), "cb_mlm_loss_fwd")
+    return lse
+
+
+def mlm_loss_bwd(logits: torch.Tensor, lse: torch.Tensor, sel: MlmSelection, dloss_rows: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """cb_mlm_loss_bwd: the (cap, V) view of a new (cap, ldd) ``dtype`` buffer (ldd = V rounded up to 16 bytes) holding d(loss)/d(logits)
+    scaled by dloss_rows (B * Lt,) fp32 -- the A operand of the decoder's two backward GEMMs."""
+    cap, v = logits.shape
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and cap == sel.cap and v == sel.v
+    assert dloss_rows.dtype == torch.float32 and dloss_rows.is_contiguous() and dloss_rows.numel() == sel.rows
+    per16 = 8 if dtype == torch.bfloat16 else 4
+    ldd = (v + per16 - 1) // per16 * per16
+    store = torch.empty(cap, ldd, dtype=dtype, device=logits.device)
+    _chk(_lib.get().cb_mlm_loss_bwd(dtype_code(dtype), _ptr(logits), logits.stride(0), _ptr(lse), _ptr(sel.slot_row), _ptr(sel.slot_label),
+                                    sel.ignore_index, _ptr(dloss_rows), _ptr(store), ldd, cap, v, _stream(logits)), "cb_mlm_loss_bwd")
+    return store[:, :v]
+
+
 LOSS_MSE, LOSS_BCE, LOSS_RANK = 0, 1, 2
 
 

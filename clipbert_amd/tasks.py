@@ -104,8 +104,31 @@ def set_learning_rates(optimizer, cfg, global_step: int, n_epoch: int = 0):
     return lr_t, lr_c
 
 
+def _pretrain_forward(model, batch: Dict, cfg) -> Dict:
+    """forward_step of src/pretrain/run_pretrain.py:196-202, with the masked-LM head in the mode cfg.mlm_rows names ("labelled" unless the
+    config says "all"; cfg.mlm_capacity = fixed number of slots, None = every text row fits).  A batch without mlm_labels runs "all"."""
+    mini = {k: v for k, v in batch.items() if k not in ("caption_ids", "vid_id", "question_ids")}
+    mini["n_examples_list"] = list(mini["n_examples_list"])
+    if not _get(cfg, "use_itm", True):
+        mini["itm_labels"] = None
+    mini["mlm_rows"] = _get(cfg, "mlm_rows", "labelled") if mini.get("mlm_labels") is not None else "all"
+    mini["mlm_capacity"] = _get(cfg, "mlm_capacity")
+    return model(mini)
+
+
+def pretrain_loss(model, batch: Dict, cfg) -> torch.Tensor:
+    """The loss of the pretraining loop (run_pretrain.py:386-395): mlm_loss.mean() if cfg.use_mlm, plus itm_loss.mean() if cfg.use_itm.
+    A ``loss_fn`` for train_step / start_training."""
+    out = _pretrain_forward(model, batch, cfg)
+    parts = [clips.mean_loss(out[k]) for k, flag in (("mlm_loss", "use_mlm"), ("itm_loss", "use_itm"))
+             if _get(cfg, flag, True) and torch.is_tensor(out[k])]
+    if not parts:
+        raise ValueError("pretrain_loss: neither cfg.use_mlm nor cfg.use_itm leaves a loss (or the batch carries no labels for it)")
+    return parts[0] if len(parts) == 1 else parts[0] + parts[1]
+
+
 def train_step(model, optimizer, batch: Dict, cfg, global_step: int, sync=None, n_epoch: int = 0, micro_step: int = 0,
-               fold_clips: bool = True) -> torch.Tensor:
+               fold_clips: bool = True, loss_fn=None) -> torch.Tensor:
     """One micro-step of start_training (:380-494): forward over the clips, pooled loss, backward; on the last micro-step of
     a gradient-accumulation group ((micro_step + 1) % cfg.gradient_accumulation_steps == 0, :426-436) also the gradient
     all-reduce (``sync`` = clipbert_amd.dist.GradSync or None), the LR schedule and clip + AdamW.  Gradients of the
@@ -114,7 +137,9 @@ def train_step(model, optimizer, batch: Dict, cfg, global_step: int, sync=None, 
     With ``rt.after_encoder_backward = sync.reduce_transformer`` the transformer buckets are issued from inside the LAST encoder
     backward of the group (the model counts its pending encoder nodes, so an un-folded clip loop does not fire early) and travel
     during the ResNet backward; with ``rt.after_res5_backward = sync.reduce_cnn_early`` (after ``sync.set_cnn_split``) the
-    grid_encoder + res5 part of the CNN range follows from inside the last ResNet backward, while res4 / res3 still run."""
+    grid_encoder + res5 part of the CNN range follows from inside the last ResNet backward, while res4 / res3 still run.
+
+    ``loss_fn``: loss = loss_fn(model, batch, cfg) replaces the clip stack and the pooled loss (pretrain_loss: the pretraining loop)."""
     acc = max(1, int(_get(cfg, "gradient_accumulation_steps", 1) or 1))
     first, last = micro_step % acc == 0, (micro_step + 1) % acc == 0
     if first:
@@ -126,8 +151,11 @@ def train_step(model, optimizer, batch: Dict, cfg, global_step: int, sync=None, 
         rt.after_encoder_backward = None                    # no exchange before the group is complete
         rt.after_res5_backward = None
     try:
-        stack = forward_clips_stack(model, batch, _get(cfg, "train_n_clips", 1), _get(cfg, "num_frm"), fold=fold_clips, cfg=cfg)
-        loss = training_loss(model, stack, batch["labels"], batch["n_examples_list"], _get(cfg, "score_agg_func", "mean"))
+        if loss_fn is not None:
+            loss = loss_fn(model, batch, cfg)
+        else:
+            stack = forward_clips_stack(model, batch, _get(cfg, "train_n_clips", 1), _get(cfg, "num_frm"), fold=fold_clips, cfg=cfg)
+            loss = training_loss(model, stack, batch["labels"], batch["n_examples_list"], _get(cfg, "score_agg_func", "mean"))
         loss.backward()
     finally:
         rt.after_encoder_backward, rt.after_res5_backward = hook, hook5
@@ -200,8 +228,47 @@ def validate_retrieval(model, val_loader, eval_videos, cfg, gt_txt_id2vid_id=Non
     return log
 
 
+@torch.no_grad()
+def validate_pretrain(model, val_loader, cfg, group=None) -> Dict[str, float]:
+    """validate of src/pretrain/run_pretrain.py:205-273: masked-LM loss / accuracy per labelled token and ITM loss / accuracy per example
+    over ``val_loader``, sums over the ranks.  In the labelled-rows mode the arg-max comes from ``mlm_pred``; in "all" mode it is the
+    reference's own expression on ``mlm_scores`` (:233-237).  A fixed cfg.mlm_capacity that a batch overflowed is an error here, where
+    the losses are read back anyway: the dropped rows would be missing from every number."""
+    was_training = model.training
+    model.eval()
+    use_mlm, use_itm = _get(cfg, "use_mlm", True), _get(cfg, "use_itm", True)
+    mlm_loss, n_tok, n_tok_ok, itm_loss, n_ex, n_ex_ok = 0.0, 0, 0, 0.0, 0, 0
+    for batch in val_loader:
+        out = _pretrain_forward(model, batch, cfg)
+        labels = out["mlm_labels"]
+        if use_mlm and labels is not None:
+            mlm_loss += float(out["mlm_loss"].sum().item())
+            mask = labels != -100
+            n_tok += int(mask.sum().item())
+            if out["mlm_scores"] is None:
+                if _get(cfg, "mlm_capacity") is not None and int(model.transformer.mlm_counts[1].item()) != 0:
+                    raise RuntimeError(f"validate_pretrain: cfg.mlm_capacity = {_get(cfg, 'mlm_capacity')} slots dropped "
+                                       f"{int(model.transformer.mlm_counts[1].item())} labelled rows")
+                n_tok_ok += int((out["mlm_pred"][mask] == labels[mask]).sum().item())
+            else:
+                n_tok_ok += int((out["mlm_scores"][mask].max(dim=-1)[1] == labels[mask]).sum().item())
+        if use_itm:
+            itm_loss += float(out["itm_loss"].sum().item())
+            n_ex += len(out["itm_labels"])
+            n_ex_ok += int((out["itm_scores"].max(dim=-1)[1] == out["itm_labels"]).sum().item())
+    mlm_loss, n_tok, n_tok_ok = _all_sum(mlm_loss, group), _all_sum(n_tok, group), _all_sum(n_tok_ok, group)
+    itm_loss, n_ex, n_ex_ok = _all_sum(itm_loss, group), _all_sum(n_ex, group), _all_sum(n_ex_ok, group)
+    model.train(was_training)
+    log = {"valid/mlm_loss": 0, "valid/mlm_acc": 0, "valid/itm_loss": 0, "valid/itm_acc": 0}
+    if n_tok != 0:
+        log.update({"valid/mlm_loss": float(mlm_loss / n_tok), "valid/mlm_acc": float(n_tok_ok / n_tok)})
+    if n_ex != 0:
+        log.update({"valid/itm_loss": float(itm_loss / n_ex), "valid/itm_acc": float(n_ex_ok / n_ex)})
+    return log
+
+
 def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=None, model_saver=None, restorer=None,
-                   total_n_examples: Optional[int] = None, fold_clips: bool = True, log_fn=None, overlap: bool = True) -> int:
+                   total_n_examples: Optional[int] = None, fold_clips: bool = True, log_fn=None, overlap: bool = True, loss_fn=None) -> int:
     """The loop of start_training (run_video_retrieval.py:379-516 / run_video_qa.py:457-560) around train_step: infinite
     iteration over ``train_loader`` until cfg.num_train_steps optimizer steps, gradient accumulation, LR schedules with the
     multi-step epoch counter, validation + ``model_step_N.pt`` every cfg.valid_steps (and once at the end), restorer.step()
@@ -212,7 +279,9 @@ def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=N
     Ranks: pass ``model_saver`` / ``restorer`` on EVERY rank (clipbert_amd.checkpoint: both write on rank 0 only, the restorer
     restores on all ranks -- the reference's order, run_video_retrieval.py:329-346).  All ranks must run the same number of
     optimizer steps: the resumed global step is agreed on across the ranks (max), and when the ranks did not all restore the
-    same step, the most advanced rank's parameters, AdamW moments and optimizer step count are broadcast before the first step."""
+    same step, the most advanced rank's parameters, AdamW moments and optimizer step count are broadcast before the first step.
+
+    ``loss_fn``: handed to every train_step (see there)."""
     from .data import InfiniteIterator
     if sync is not None and sync.world > 1 and overlap and model.rt is not None and model.rt.after_encoder_backward is None:
         sync.attach(model)
@@ -250,7 +319,8 @@ def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=N
         return global_step
     for micro, batch in enumerate(InfiniteIterator(train_loader)):
         n_epoch = int(1.0 * total_bsz * (global_step + 1) / total_n_examples) if total_n_examples else 0
-        loss = train_step(model, optimizer, batch, cfg, global_step, sync=sync, n_epoch=n_epoch, micro_step=micro, fold_clips=fold_clips)
+        loss = train_step(model, optimizer, batch, cfg, global_step, sync=sync, n_epoch=n_epoch, micro_step=micro, fold_clips=fold_clips,
+                          loss_fn=loss_fn)
         if (micro + 1) % acc != 0:
             continue
         global_step += 1

@@ -363,6 +363,39 @@ int cb_attention_bwd(int32_t dtype, const void* qkv, const float* key_mask, cons
 int cb_cross_entropy(const float* logits, int64_t ld, const int64_t* labels, float* loss, float* dlogits,
                      const float* dloss, int64_t rows, int32_t C, int64_t ignore_index, void* stream);
 
+/* ---- masked-LM head over the LABELLED rows only ------------------------------------------------------------------------------------
+ * BertLMPredictionHead (src/modeling/transformers.py:497-515) and the masked-LM CrossEntropyLoss(reduction="none", ignore_index=-100)
+ * of ClipBertForPreTraining.forward (src/modeling/modeling.py:283-299) are only ever consumed at the ~15 % of text rows that
+ * mask_batch_text_tokens labelled: the loss of every other row is 0 and so is its gradient.  cb_mlm_select compacts the labelled rows ON THE
+ * DEVICE (no host read of the count) into `cap` slots that cb_gemm's gather / row-map modes address; the transform, LayerNorm and decoder
+ * then run on (cap, .) matrices, and the two loss kernels below work on the compact fp32 logits (cap, V).
+ *
+ * cb_mlm_select: labels int64 [rows = B * Lt] of the text rows (b, t) of a (B, L, d) sequence buffer (text row (b, t) at element
+ * (b * L + t) * d).  A row is labelled when its label is neither ignore_index nor outside [0, V).  Slots j < min(count, cap), labelled
+ * rows in ASCENDING row order: slot_row[j] = the row in [0, rows); slot_label[j]; tab[j] = {(b L + t) d, 0, t} -- a_tab (CB_ROWK_GATHER)
+ * or b_tab (CB_KROW_GATHER) of a one-tap gather with R = S = 1, Cin = d, H = 1, W = Lt; c_rowmap[j] = b L + t.  The remaining slots are
+ * padding: slot_row -1, label ignore_index, a table entry that fails the gather's bounds test (the row reads as zeros), and
+ * c_rowmap = B * L: a DUMP row behind the real ones -- a matrix scattered through c_rowmap has B * L + 1 rows.  counts[0] = count;
+ * counts[1] += max(0, count - cap): rows dropped because more were labelled than there are slots (the first cap in order are kept; the
+ * caller zeroes counts[1] once).  loss_rows[r] = 0 and pred_rows[r] = -100 for EVERY r < rows, so that the two per-row outputs of
+ * cb_mlm_loss_fwd are fully defined without a fill.  One workgroup (a few thousand rows at most). */
+int cb_mlm_select(const int64_t* labels, int64_t ignore_index, int32_t rows, int32_t Lt, int32_t L, int32_t d, int32_t V, int32_t cap,
+                  int32_t* slot_row, int64_t* slot_label, cb_pixel* tab, int32_t* c_rowmap, int64_t* counts, float* loss_rows,
+                  int64_t* pred_rows, void* stream);
+/* Per slot of the compact logits (cap, V), fp32, row stride ld >= V (the columns V..ld-1 are never read), ONE pass:
+ * lse[j] = logsumexp(x[j, :]); loss_rows[slot_row[j]] = lse[j] - x[j, slot_label[j]] (modeling.py:287-298);
+ * pred_rows[slot_row[j]] = argmax_c x[j, c], the lowest index among equals -- what the validation of the pretraining runner takes from
+ * the full score matrix (src/pretrain/run_pretrain.py:229-237).  Padding slots write nothing. */
+int cb_mlm_loss_fwd(const float* logits, int64_t ld, const int32_t* slot_row, const int64_t* slot_label, int64_t ignore_index, int32_t cap,
+                    int32_t V, float* lse, float* loss_rows, int64_t* pred_rows, void* stream);
+/* dlogits[j, c] = dloss_rows[slot_row[j]] * (exp(x[j, c] - lse[j]) - [c == slot_label[j]]) (the autograd backward of
+ * modeling.py:287-298) in `dtype` (CB_F32 | CB_BF16; fp32 arithmetic, rounded once) into a (cap, ldd) buffer, ldd >= V: the A operand
+ * of the decoder's data- and weight-gradient GEMMs (transformers.py:504-515 under autograd) as it is -- no fp32 gradient matrix, no
+ * cast.  Padding slots receive zeros over the whole row (their columns enter the weight gradient's reduction), and so do the columns
+ * V..ldd-1 of every row. */
+int cb_mlm_loss_bwd(int32_t dtype, const float* logits, int64_t ld, const float* lse, const int32_t* slot_row, const int64_t* slot_label,
+                    int64_t ignore_index, const float* dloss_rows, void* dlogits, int64_t ldd, int32_t cap, int32_t V, void* stream);
+
 /* Column sums: out[n] (+)= sum_m g[m,n]  (bias gradients).  fp32 atomics into out. */
 int cb_colsum(int32_t dtype, const void* g, int64_t ldg, float* out, int64_t M, int32_t N, void* stream);
 
@@ -481,7 +514,8 @@ const char* cb_last_error(void);
  *     cb_gemm_group takes strided batches / a_rowsum on the unsplit bf16 weight-gradient form; cb_stem_pool_u8; cb_zero_ranges;
  * 8 = cb_resize_pack_u8 (raw-frame ingest: resize + pad + ImageNorm of native-resolution uint8 frames; nothing else changed);
  * 9 = cb_optim_step (CB_OPT_ADAM / CB_OPT_ADAMAX beside AdamW: the reference's other two cfg.optim choices; nothing else changed);
- * 10 = cb_resize_pack_yuv420 (the raw-frame ingest from I420 / NV12 planes; nothing else changed) */
+ * 10 = cb_resize_pack_yuv420 (the raw-frame ingest from I420 / NV12 planes; nothing else changed);
+ * 11 = cb_mlm_select, cb_mlm_loss_fwd, cb_mlm_loss_bwd (the masked-LM head over the labelled rows only; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
