@@ -5,6 +5,7 @@ the 2-deep reduction) plus ragged ones."""
 import pytest
 import torch
 
+import dropout_restatement as DR
 from clipbert_amd import ops
 
 BF = torch.bfloat16
@@ -53,6 +54,44 @@ def test_pooler_form_strided_rows_f32_out_and_residual(hw):
     o32 = torch.empty(B, 2, dtype=torch.float32, device=hw.dev)
     ops.gemm(seq, w2, B, 2, d, out=o32, lda=L * d, tile=9)
     close(o32, seq[:, 0].float() @ w2.float().t(), d)
+
+
+def _dropout_epilogue(hw, a, w, b, res, a_rows, M, N, K, **lda):
+    """tile 9: tanh(a W^T + b) * m (+ residual) against fp64 with the restated mask of an (M, N) site; a_rows: the rows of A as fp64"""
+    p, seed, word = 0.3, 41, 1 << 33
+    sp = torch.tensor([word], dtype=torch.int64, device=hw.dev)
+    kw = dict(shift=b, act=ops.ACT_TANH, dropout_p=p, dropout_seed=seed, seed_ptr=sp, tile=9, **lda)
+    act = torch.tanh(a_rows @ w.double().cpu().t() + b.double().cpu())
+    keep = DR.keep_mask(DR.effective_seed(seed, word), M, N, p)
+    m = keep.double() * DR.multiplier(p)
+    out = torch.empty(M, N, dtype=BF, device=hw.dev)
+    assert ops.gemm_plan(a, w, M, N, K, out=out, residual=res, **kw)[0] == 9
+    ops.gemm(a, w, M, N, K, out=out, residual=res, **kw)
+    close(out.cpu(), (act * m + res.double().cpu()).float(), K)
+    assert float(act.abs().min()) > 1e-6                         # the undropped reference has no zero ...
+    bare = torch.empty(M, N, dtype=BF, device=hw.dev)
+    ops.gemm(a, w, M, N, K, out=bare, **kw)
+    assert torch.equal((bare != 0).cpu(), keep)                  # ... so what is zero was dropped
+    close(bare.cpu(), (act * m).float(), K)
+
+
+@pytest.mark.parametrize("N", [72, 68, 70])                   # 8-wide epilogue; element epilogue with N % 4 == 0 and with ceil(N / 4) != N / 4
+def test_epilogue_dropout_against_restated_mask(hw, N):
+    """the pooler's training epilogue on tile 9 (bias -> tanh -> dropout -> residual) against fp64 with the mask restated from
+    csrc/common.h (tests/dropout_restatement.py); two row blocks, a K tail"""
+    M, K = 33, 200
+    x, w, b = hw(rnd(M, K, seed=1, scale=0.5).to(BF)), hw(rnd(N, K, seed=2, scale=0.2).to(BF)), hw(rnd(N, seed=3))
+    res = hw(rnd(M, N, seed=4).to(BF))
+    _dropout_epilogue(hw, x, w, b, res, x.double().cpu(), M, N, K)
+
+
+def test_pooler_form_dropout_against_restated_mask(hw):
+    """the same with A = the first token of every sequence (lda = L * d), as encoder_forward launches the pooler in training"""
+    B, L, d = 24, 5, 64
+    seq = hw(rnd(B, L, d, seed=1).to(BF))
+    w, b = hw(rnd(48, d, seed=2, scale=0.2).to(BF)), hw(rnd(48, seed=3))
+    res = hw(rnd(B, 48, seed=4).to(BF))
+    _dropout_epilogue(hw, seq, w, b, res, seq[:, 0].double().cpu(), B, 48, d, lda=L * d)
 
 
 @pytest.mark.parametrize("M,N,K", [(64, 768, 1536), (64, 1536, 2), (64, 768, 768), (40, 72, 100), (7, 8, 3)])

@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import dropout_restatement as DR
 from clipbert_amd import ops
 
 BF = torch.bfloat16
@@ -81,6 +82,58 @@ def test_split_k_slabs_any_epilogue(hw, tile, sched):
     dwa = torch.zeros(M, N, dtype=torch.float32, device=hw.dev)
     ops.gemm(x, w, M, N, K, out=dwa, accumulate=True, tile=tile, split_k=2, splitk_ws=torch.empty(4, dtype=torch.float32, device=hw.dev))
     torch.testing.assert_close(dwa, x.float() @ w.float().t(), **TOL)
+
+
+@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("M,N,K,split", [(300, 264, 104, 1), (300, 72, 104, 1), (200, 136, 320, 2)])
+def test_epilogue_dropout_against_restated_mask(hw, tile, M, N, K, split):
+    """tanh(x W^T + b) * m + residual on the 8-wave tiles (ragged M and N edges; the K split's slab-reduce epilogue) against fp64 with
+    the mask restated from csrc/common.h (tests/dropout_restatement.py): the mask addressing row * ceil(N / 4) + col / 4 of the
+    8-column epilogue and the order bias -> activation -> dropout -> residual.  Without the residual the non-zero outputs are the
+    restated keep mask exactly."""
+    p, seed, word = 0.3, 23, 987654321
+    sp = torch.tensor([word], dtype=torch.int64, device=hw.dev)
+    x, w, b = hw(rnd(M, K, seed=1, scale=0.5).to(BF)), hw(rnd(N, K, seed=2, scale=0.2).to(BF)), hw(rnd(N, seed=3))
+    res = hw(rnd(M, N, seed=4).to(BF))
+    kw = dict(shift=b, act=ops.ACT_TANH, dropout_p=p, dropout_seed=seed, seed_ptr=sp, tile=tile, split_k=split, splitk_ws=ws(hw))
+    act = torch.tanh(x.double().cpu() @ w.double().cpu().t() + b.double().cpu())
+    keep = DR.keep_mask(DR.effective_seed(seed, word), M, N, p)
+    m = keep.double() * DR.multiplier(p)
+    out = torch.empty(M, N, dtype=BF, device=hw.dev)
+    assert ops.gemm_plan(x, w, M, N, K, out=out, residual=res, **kw)[:2] == (tile, split)           # the kernel under test runs
+    ops.gemm(x, w, M, N, K, out=out, residual=res, **kw)
+    torch.testing.assert_close(out.double().cpu(), act * m + res.double().cpu(), **TOL)
+    assert float(act.abs().min()) > 1e-6                         # the undropped reference has no zero ...
+    bare = torch.empty(M, N, dtype=BF, device=hw.dev)
+    ops.gemm(x, w, M, N, K, out=bare, **kw)
+    assert torch.equal((bare != 0).cpu(), keep)                  # ... so what is zero was dropped
+    torch.testing.assert_close(bare.double().cpu(), act * m, **TOL)
+
+
+@pytest.mark.parametrize("tile", TILES)
+@pytest.mark.parametrize("N", [264, 72])                      # a full tile and a last 8-column chunk; one narrow tile
+def test_training_epilogue_dropout_against_restated_mask(hw, tile, N):
+    """What BertSelfOutput / BertOutput launch in bf16 training: bias + dropout + residual with NO activation, contiguous aligned bf16
+    output and residual -- the option combination with a specialised epilogue body (gemm_impl.h FAST_EPI_COMBOS[4]; the tanh of the case
+    above goes through the generic epilogue8 instead).  (x W^T + b) * m + residual against fp64 with the restated mask; with an all-zero
+    residual the call stays on that combination and the non-zero outputs are the restated keep mask exactly."""
+    M, K, p, seed, word = 300, 104, 0.3, 29, 123456789
+    sp = torch.tensor([word], dtype=torch.int64, device=hw.dev)
+    x, w, b = hw(rnd(M, K, seed=1, scale=0.5).to(BF)), hw(rnd(N, K, seed=2, scale=0.2).to(BF)), hw(rnd(N, seed=3))
+    res = hw(rnd(M, N, seed=4).to(BF))
+    kw = dict(shift=b, dropout_p=p, dropout_seed=seed, seed_ptr=sp, tile=tile)
+    pre = x.double().cpu() @ w.double().cpu().t() + b.double().cpu()
+    keep = DR.keep_mask(DR.effective_seed(seed, word), M, N, p)
+    m = keep.double() * DR.multiplier(p)
+    out = torch.empty(M, N, dtype=BF, device=hw.dev)
+    assert ops.gemm_plan(x, w, M, N, K, out=out, residual=res, **kw)[:2] == (tile, 1)               # the kernel under test runs
+    ops.gemm(x, w, M, N, K, out=out, residual=res, **kw)
+    torch.testing.assert_close(out.double().cpu(), pre * m + res.double().cpu(), **TOL)
+    assert float(pre.abs().min()) > 1e-6                         # the undropped reference has no zero ...
+    bare = torch.empty(M, N, dtype=BF, device=hw.dev)
+    ops.gemm(x, w, M, N, K, out=bare, residual=torch.zeros_like(res), **kw)
+    assert torch.equal((bare != 0).cpu(), keep)                  # ... so what is zero was dropped
+    torch.testing.assert_close(bare.double().cpu(), pre * m, **TOL)
 
 
 @pytest.mark.parametrize("tile", TILES)

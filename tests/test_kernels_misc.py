@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import dropout_restatement as DR
 from clipbert_amd import ops
 from oracle import clipbert_oracle as O
 
@@ -269,6 +270,155 @@ def test_dropout_kernel_and_seed_pointer(hw):
     torch.testing.assert_close(a[a > 0], torch.full_like(a[a > 0], 1 / 0.9))
     c = ops.dropout(x, 0.1, seed=4)
     assert not torch.equal(a, c)
+
+
+def seed_word(v):
+    return torch.tensor([v], dtype=torch.int64, device=DEV[0])
+
+
+@pytest.mark.parametrize("dt", DT)
+def test_dropout_kernel_equals_the_restated_mask(hw, dt):
+    """cb_dropout against tests/dropout_restatement.py (written from the comment block of csrc/common.h): the dropped set is the
+    restated one exactly, kept values are x * float32(1 / (1 - p)) (bit for bit in fp32); vector body and the 1..3 element tail;
+    p = 1e-6 has threshold 0: nothing drops, the scale still applies; in place; the seed is dropout_seed + *seed_ptr."""
+    seed, word = 12345, 6789
+    sp = seed_word(word)
+    for n in (1, 3, 4, 7, 5001):
+        x = (rnd(n, seed=n).abs() + 0.5).to(dt)                       # no zeros: y != 0 <=> kept
+        for p in (0.1, 0.5, 1e-6):
+            keep = DR.keep_mask(DR.effective_seed(seed, word), 1, n, p).view(n).to(DEV[0])
+            mult = torch.tensor(DR.multiplier(p), dtype=torch.float32, device=DEV[0])
+            y = ops.dropout(x, p, seed=seed, seed_ptr=sp)
+            assert torch.equal(y != 0, keep), (n, p)
+            want = torch.where(keep, x.float() * mult, torch.zeros((), device=DEV[0]))
+            if dt == torch.float32:
+                assert torch.equal(y, want), (n, p)
+            else:
+                torch.testing.assert_close(y.float(), want, **tol(dt))
+            if p == 1e-6:
+                assert DR.threshold(p) == 0 and bool(keep.all())
+            z = x.clone()
+            assert ops.dropout(z, p, seed=seed, seed_ptr=sp, out=z) is z and torch.equal(z, y), (n, p)      # in place
+            assert torch.equal(ops.dropout(x, p, seed=seed + word), y)                                      # seed + *seed_ptr
+    # the 2-D form of a site with cols % 4 == 0 is the flat stream
+    assert torch.equal(DR.keep_mask(77, 6, 8, 0.3).view(-1), DR.keep_mask(77, 1, 48, 0.3).view(-1))
+
+
+def _epilogue_case(M, N, K, dt):
+    """inputs of out = tanh(x W^T + b) * m + residual and the fp64 pre-dropout activation"""
+    x, w, b = rnd(M, K, seed=1, scale=0.5).to(dt), rnd(N, K, seed=2, scale=0.2).to(dt), rnd(N, seed=3)
+    res = rnd(M, N, seed=4).to(dt)
+    act = torch.tanh(x.double() @ w.double().t() + b.double())
+    return x, w, b, res, act
+
+
+@pytest.mark.parametrize("dt", DT)
+@pytest.mark.parametrize("N", [72, 68, 70])                   # 8-wide path, 4-wide path, element path (ceil(N / 4) matters)
+@pytest.mark.parametrize("tile", [1, 2, 3, 4])
+def test_gemm_epilogue_dropout_against_restated_mask(hw, dt, N, tile):
+    """cb_gemm's 4-wave kernels: tanh(x W^T + b) * m + residual against fp64 with the restated mask -- pins the mask addressing
+    (row * ceil(N / 4) + col / 4) of every vector width AND the order bias -> activation -> dropout -> residual.  Without the residual the
+    set of non-zero outputs is the restated keep mask exactly.  (fp32 has the 64x64 tile only: every request runs it.)"""
+    M, K, p, seed, word = 150, 96, 0.3, 31, 4242
+    sp = seed_word(word)
+    x, w, b, res, act = _epilogue_case(M, N, K, dt)
+    kw = dict(shift=b, act=ops.ACT_TANH, dropout_p=p, dropout_seed=seed, seed_ptr=sp, tile=tile)
+    keep = DR.keep_mask(DR.effective_seed(seed, word), M, N, p)
+    m = keep.double() * DR.multiplier(p)
+    out = torch.empty(M, N, dtype=dt, device=DEV[0])
+    assert ops.gemm_plan(x, w, M, N, K, out=out, residual=res, **kw)[0] == (tile if dt == torch.bfloat16 else 2)
+    ops.gemm(x, w, M, N, K, out=out, residual=res, **kw)
+    torch.testing.assert_close(out.double().cpu(), act.cpu() * m + res.double().cpu(), **tol(dt))
+    assert float(act.abs().min()) > 1e-6                         # the undropped reference has no zero ...
+    bare = torch.empty(M, N, dtype=dt, device=DEV[0])
+    ops.gemm(x, w, M, N, K, out=bare, **kw)
+    assert torch.equal((bare != 0).cpu(), keep)                  # ... so what is zero was dropped
+    torch.testing.assert_close(bare.double().cpu(), act.cpu() * m, **tol(dt))
+
+
+@pytest.mark.parametrize("N", [72, 264])                      # one chunk row; two 128-column tiles and a last 8-column chunk
+@pytest.mark.parametrize("tile", [1, 2, 3, 4])
+def test_gemm_training_epilogue_dropout_against_restated_mask(hw, N, tile):
+    """What BertSelfOutput / BertOutput launch in bf16 training (encoder_forward): bias + dropout + residual with NO activation, contiguous
+    16-byte-aligned bf16 output and residual, N % 8 == 0 -- the option combination that has a specialised epilogue body of its own
+    (gemm_impl.h FAST_EPI_COMBOS[4], fast_epilogue: own mask group, own dropout-then-residual code; a tanh sends a call to the generic
+    epilogue instead).  (x W^T + b) * m + residual against fp64 with the restated mask; with an all-zero residual the call stays on that
+    body and the non-zero outputs are the restated keep mask exactly."""
+    dt = torch.bfloat16
+    M, K, p, seed, word = 150, 96, 0.3, 37, 5150
+    sp = seed_word(word)
+    x, w, b = rnd(M, K, seed=1, scale=0.5).to(dt), rnd(N, K, seed=2, scale=0.2).to(dt), rnd(N, seed=3)
+    res = rnd(M, N, seed=4).to(dt)
+    pre = (x.double() @ w.double().t() + b.double()).cpu()
+    kw = dict(shift=b, dropout_p=p, dropout_seed=seed, seed_ptr=sp, tile=tile)
+    keep = DR.keep_mask(DR.effective_seed(seed, word), M, N, p)
+    m = keep.double() * DR.multiplier(p)
+    out = torch.empty(M, N, dtype=dt, device=DEV[0])
+    assert ops.gemm_plan(x, w, M, N, K, out=out, residual=res, **kw)[0] == tile
+    ops.gemm(x, w, M, N, K, out=out, residual=res, **kw)
+    torch.testing.assert_close(out.double().cpu(), pre * m + res.double().cpu(), **tol(dt))
+    assert float(pre.abs().min()) > 1e-6                         # the undropped reference has no zero ...
+    bare = torch.empty(M, N, dtype=dt, device=DEV[0])
+    ops.gemm(x, w, M, N, K, out=bare, residual=torch.zeros_like(res), **kw)
+    assert torch.equal((bare != 0).cpu(), keep)                  # ... so what is zero was dropped
+    torch.testing.assert_close(bare.double().cpu(), pre * m, **tol(dt))
+
+
+@pytest.mark.parametrize("dt", DT)
+@pytest.mark.parametrize("rows,D", [(150, 72), (150, 768), (1100, 72), (1100, 768)])       # >= 1024 rows: the 16-wave backward
+def test_layernorm_bwd_dropout_against_restated_mask(hw, dt, rows, D):
+    """cb_layernorm_bwd / cb_layernorm_bwd_part: dx against fp64 autograd, the second output (the gradient under the dropout of the
+    GEMM that fed the LayerNorm) = dx * m with the restated mask of a (rows, D) site."""
+    p, seed, word = 0.3, 19, 1 << 40
+    sp = seed_word(word)
+    x = rnd(rows, D, seed=1).to(dt)
+    g, b = 1 + rnd(D, seed=2, scale=0.1), rnd(D, seed=3, scale=0.1)
+    dy = rnd(rows, D, seed=4).to(dt)
+    _, mean, rstd = ops.layernorm_fwd(x, g, b, 1e-12, save_stats=True)
+    xr = x.double().cpu().requires_grad_(True)
+    gr = g.double().cpu().requires_grad_(True)
+    F.layer_norm(xr, (D,), gr, b.double().cpu(), 1e-12).backward(dy.double().cpu())
+    keep = DR.keep_mask(DR.effective_seed(seed, word), rows, D, p)
+    m = keep.double() * DR.multiplier(p)
+    dgam, dbet = zeros(D), zeros(D)
+    part = torch.full((ops.ln_part_blocks(rows), 2, D), float("nan"), dtype=torch.float32, device=DEV[0])
+    for dx, dx2 in (ops.layernorm_bwd(dy, x, g, mean, rstd, dgam, dbet, dropout_p=p, dropout_seed=seed, seed_ptr=sp),
+                    ops.layernorm_bwd_part(dy, x, g, mean, rstd, part, dropout_p=p, dropout_seed=seed, seed_ptr=sp)):
+        torch.testing.assert_close(dx.double().cpu(), xr.grad, **tol(dt, 1e-4))
+        assert torch.equal((dx2 != 0).cpu(), keep & (dx != 0).cpu()) and bool((dx != 0).all())     # the dropped set, exactly
+        if dt == torch.float32:
+            torch.testing.assert_close(dx2.double().cpu(), dx.double().cpu() * m, rtol=1e-6, atol=1e-6)
+        else:
+            torch.testing.assert_close(dx2.double().cpu(), xr.grad * m, **tol(dt, 1e-4))
+    torch.testing.assert_close(dgam.double().cpu(), gr.grad, **tol(dt, 1e-4, 5e-2))
+    torch.testing.assert_close(part[:, 0].sum(0).double().cpu(), gr.grad, **tol(dt, 1e-4, 5e-2))
+
+
+@pytest.mark.parametrize("dt", DT)
+@pytest.mark.parametrize("L", [9, 41, 64, 69, 112, 169, 192, 200])      # <= 64 one-wave MFMA, 65..192 LDS-resident MFMA (bf16); 200: generic
+def test_attention_dropout_against_restated_mask(hw, dt, L):
+    """cb_attention_fwd / _bwd with dropout on the probabilities against fp64: ctx = (softmax(s) * m) @ v with the restated mask of a
+    (B * H * L, L) site -- row (b * H + h) * L + i, H odd so that a b / h mix-up shows --, lse = logsumexp(s) (dropout does not enter
+    it), dqkv = autograd through that expression.  Tolerances of test_attention_fwd_bwd."""
+    B, H, seed, word = 2, 3, 5, 11
+    sp = seed_word(word)
+    qkv = rnd(B * L, 3 * H * 64, seed=1).to(dt)
+    dctx = rnd(B * L, H * 64, seed=2).to(dt)
+    mask = ones(B, L)
+    mask[0, L - 3:] = 0
+    mask[1, 2] = 0
+    for p in (0.3, 0.1):
+        ctx, lse = ops.attention_fwd(qkv, mask, B, L, H, save_lse=True, dropout_p=p, dropout_seed=seed, seed_ptr=sp)
+        dqkv = ops.attention_bwd(qkv, mask, ctx, dctx, lse, B, L, H, dropout_p=p, dropout_seed=seed, seed_ptr=sp)
+        x = qkv.double().cpu().requires_grad_(True)
+        q, k, v = [t.view(B, L, H, 64).permute(0, 2, 1, 3) for t in x.view(B, L, 3, H * 64).unbind(2)]
+        s = q @ k.transpose(-1, -2) / 8.0 + ((1 - mask.double().cpu()) * -10000.0)[:, None, None, :]
+        m = DR.attention_mult(DR.effective_seed(seed, word), B, H, L, p)
+        ref = ((torch.softmax(s, -1) * m) @ v).permute(0, 2, 1, 3).reshape(B * L, H * 64)
+        torch.testing.assert_close(ctx.double().cpu(), ref.detach(), **tol(dt, 1e-5))
+        torch.testing.assert_close(lse.double().cpu().view(B, H, L), torch.logsumexp(s, -1).detach(), rtol=1e-4, atol=1e-4)
+        ref.backward(dctx.double().cpu())
+        torch.testing.assert_close(dqkv.double().cpu(), x.grad, **tol(dt, 1e-4, 3e-2))
 
 
 @pytest.mark.parametrize("N", [72, 68, 200])

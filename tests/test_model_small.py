@@ -2,11 +2,15 @@
 product Python layer against the CPU oracle and its autograd gradients.  Small widths / 2 layers /
 64x128 frames keep the host-emulator run to seconds; the same cases run on the GPU (marked `gpu`), and
 the full-size parity runs live in test_gpu_full.py."""
+import numpy as np
 import pytest
 import torch
 
+import dropout_restatement as DR
+import parity_bounds as PB
 from clipbert_amd import modeling as M
 from clipbert_amd import synthetic as S
+from clipbert_amd.modeling import runtime as RT
 from oracle import clipbert_oracle as O
 
 SMALL = dict(O.BASE_CONFIG, hidden_size=128, num_attention_heads=2, intermediate_size=256, num_hidden_layers=2,
@@ -62,39 +66,14 @@ def grads_of_oracle(sd, batch, cfg, head, loss_fn):
     return out, sdr
 
 
-@pytest.mark.parametrize("head,extra,repeat", [
-    ("retrieval", dict(num_labels=2, loss_type="ce", margin=0.1), 2),
-    ("pretraining", dict(), 1),
-])
-def test_forward_backward_matches_oracle_fp32(hw, head, extra, repeat):
-    torch.manual_seed(0)
-    cfg, sd, model = build(head, extra, torch.float32, hw.dev)
-    n_videos, lt = 2, 6
-    batch = make_batch(cfg, head, n_videos, repeat, lt)
-    n_pairs = n_videos * repeat
-    if head == "pretraining":
-        mlm = batch["text_input_ids"].clone()
-        mlm[:, ::2] = -100
-        batch["mlm_labels"] = mlm
-        batch["itm_labels"] = S.synthetic_labels(n_pairs, 2, 5)
-        loss_fn = lambda o: o["mlm_loss"].mean() + o["itm_loss"].mean()
-    else:
-        batch["labels"] = S.synthetic_labels(n_pairs, 2, 5)
-        loss_fn = lambda o: o["loss"].mean()
-    ref, sdr = grads_of_oracle(sd, batch, cfg, head, loss_fn)
-    out = model(to_dev(batch, hw.dev))
+def forward_tol(hw):
     # the emulator shares the host libm with the oracle; on the GPU erf/exp/tanh differ in the last ulps
-    ft = dict(rtol=1e-3, atol=1e-4) if hw.name == "emul" else dict(rtol=2e-3, atol=1e-3)
+    return dict(rtol=1e-3, atol=1e-4) if hw.name == "emul" else dict(rtol=2e-3, atol=1e-3)
+
+
+def assert_grads_match_oracle(hw, model, sdr):
+    """every trainable parameter's gradient against the oracle's autograd (the leaves of ``sdr``)"""
     gt = 2e-3 if hw.name == "emul" else 5e-3
-    if head == "pretraining":
-        torch.testing.assert_close(out["itm_scores"].cpu(), ref["itm_scores"], **ft)
-        torch.testing.assert_close(out["mlm_scores"].cpu(), ref["mlm_scores"], **ft)
-        torch.testing.assert_close(out["mlm_loss"].cpu(), ref["mlm_loss"], **ft)
-    else:
-        torch.testing.assert_close(out["logits"].cpu(), ref["logits"], **ft)
-        torch.testing.assert_close(out["loss"].cpu(), ref["loss"], **ft)
-    model.rt.bank.zero_grad()
-    loss_fn(out).backward()
     checked = 0
     worst = (0.0, "")
     for name, p in model.named_parameters():
@@ -122,6 +101,205 @@ def test_forward_backward_matches_oracle_fp32(hw, head, extra, repeat):
     assert checked > 40, checked
     # frozen stem / res2 must not have been touched
     assert model.cnn.feature.backbone.stem.conv1.weight.grad is None
+
+
+@pytest.mark.parametrize("head,extra,repeat", [
+    ("retrieval", dict(num_labels=2, loss_type="ce", margin=0.1), 2),
+    ("pretraining", dict(), 1),
+])
+def test_forward_backward_matches_oracle_fp32(hw, head, extra, repeat):
+    torch.manual_seed(0)
+    cfg, sd, model = build(head, extra, torch.float32, hw.dev)
+    n_videos, lt = 2, 6
+    batch = make_batch(cfg, head, n_videos, repeat, lt)
+    n_pairs = n_videos * repeat
+    if head == "pretraining":
+        mlm = batch["text_input_ids"].clone()
+        mlm[:, ::2] = -100
+        batch["mlm_labels"] = mlm
+        batch["itm_labels"] = S.synthetic_labels(n_pairs, 2, 5)
+        loss_fn = lambda o: o["mlm_loss"].mean() + o["itm_loss"].mean()
+    else:
+        batch["labels"] = S.synthetic_labels(n_pairs, 2, 5)
+        loss_fn = lambda o: o["loss"].mean()
+    ref, sdr = grads_of_oracle(sd, batch, cfg, head, loss_fn)
+    out = model(to_dev(batch, hw.dev))
+    ft = forward_tol(hw)
+    if head == "pretraining":
+        torch.testing.assert_close(out["itm_scores"].cpu(), ref["itm_scores"], **ft)
+        torch.testing.assert_close(out["mlm_scores"].cpu(), ref["mlm_scores"], **ft)
+        torch.testing.assert_close(out["mlm_loss"].cpu(), ref["mlm_loss"], **ft)
+    else:
+        torch.testing.assert_close(out["logits"].cpu(), ref["logits"], **ft)
+        torch.testing.assert_close(out["loss"].cpu(), ref["loss"], **ft)
+    model.rt.bank.zero_grad()
+    loss_fn(out).backward()
+    assert_grads_match_oracle(hw, model, sdr)
+
+
+# ---- model.train(): every dropout site on, held to the oracle through masks restated from csrc/common.h (tests/dropout_restatement.py) ----
+_SITES = dict(emb=RT._SITE_EMB, attn=RT._SITE_ATTN, self_out=RT._SITE_SELF_OUT, out=RT._SITE_OUT, pool=RT._SITE_POOL, reg=RT._SITE_REG)
+RETRIEVAL_CE = dict(num_labels=2, loss_type="ce", margin=0.1)
+
+
+def restated_masks(cfg, fwd_i, seed_word):
+    """the hook of O.dropout_masks that drops what the product drops in its fwd_i-th training forward.  The product as it is: the
+    regression head's second dropout reads rt.forward_count AFTER the encoder advanced it."""
+    def fn(site, layer, x):
+        p = cfg["attention_probs_dropout_prob"] if site == "attn" else cfg["hidden_dropout_prob"]
+        f = fwd_i + 1 if site == "reg" else fwd_i
+        return x * DR.site_mask(_SITES[site], layer, f, seed_word, x.shape, p, dtype=x.dtype)
+    return fn
+
+
+def oracle_leaves(sd, head):
+    sdr = {k: v.clone().requires_grad_(v.is_floating_point() and "norm" not in k and "running" not in k) for k, v in sd.items()}
+    if head == "pretraining":      # tied weights share one leaf
+        sdr["transformer.cls.predictions.decoder.weight"] = sdr["transformer.bert.embeddings.word_embeddings.weight"]
+        sdr["transformer.cls.predictions.decoder.bias"] = sdr["transformer.cls.predictions.bias"]
+    return sdr
+
+
+def train_case(cfg, head, repeat, seed=5):
+    """(batch, loss_fn, names of the outputs the forward is compared on) of one head in training"""
+    # two videos: with the third one of test_regression_head_matches_oracle a ReLU pre-activation of res3.2.conv1 lies 4e-5 from zero,
+    # fp32 summation order flips it, and the res3 weight gradients move by 1e-2 of their largest element with dropout off as well
+    n_videos = 2
+    batch = make_batch(cfg, head, n_videos, repeat, 6, seed)
+    n_pairs = n_videos * repeat
+    if head == "pretraining":
+        mlm = batch["text_input_ids"].clone()
+        mlm[:, ::2] = -100
+        batch["mlm_labels"] = mlm
+        batch["itm_labels"] = S.synthetic_labels(n_pairs, 2, seed)
+        return batch, (lambda o: o["mlm_loss"].mean() + o["itm_loss"].mean()), ("itm_scores", "mlm_scores", "mlm_loss")
+    if head == "regression":
+        batch["labels"] = torch.tensor([1.0, 4.0, 2.0, 7.0])
+    else:
+        batch["labels"] = S.synthetic_labels(n_pairs, 2, seed)
+    return batch, (lambda o: o["loss"].mean()), ("logits", "loss")
+
+
+def oracle_batch(batch, head):
+    return dict(batch, training=True) if head == "regression" else dict(batch)        # (BatchNorm1d on batch statistics)
+
+
+TRAIN_CASES = [
+    ("retrieval", RETRIEVAL_CE, 2, 0),
+    ("retrieval", RETRIEVAL_CE, 2, 0x1234567890ABCDEF),            # every kernel family adds *seed_ptr to its seed
+    ("pretraining", dict(), 1, 0),                                   # (pixel_random_sampling_size unset; no pooled dropout)
+    ("regression", dict(num_labels=1, loss_type="mse"), 2, 0),       # training BatchNorm1d, the head's second dropout
+]
+
+
+@pytest.mark.parametrize("head,extra,repeat,seed_word", TRAIN_CASES)
+def test_train_mode_forward_backward_matches_masked_oracle_fp32(hw, head, extra, repeat, seed_word):
+    """model.train() with p = 0.1 at every site: logits, losses and ALL parameter gradients against the oracle with the restated masks
+    at the reference's dropout places (O.dropout_masks) -- same assertions and tolerances as the eval-mode test above.  A wrong mask
+    address, a wrong order of bias / activation / dropout / residual, a backward that regenerates another mask, a site too many or
+    too few: each costs O(1) per element against tolerances of 1e-3."""
+    cfg, sd, model = build(head, extra, torch.float32, hw.dev)
+    model.train()
+    fwd_i = 3
+    model.rt.forward_count = fwd_i
+    model.rt.seed_dev.fill_(seed_word)
+    batch, loss_fn, outs = train_case(cfg, head, repeat)
+    sdr = oracle_leaves(sd, head)
+    with O.dropout_masks(restated_masks(cfg, fwd_i, seed_word)):
+        ref = O.clipbert_forward(sdr, oracle_batch(batch, head), cfg, head)
+    loss_fn(ref).backward()
+    ft = forward_tol(hw)
+    # the check must not pass with dropout silently off on both sides: the oracle's own train-mode output is far from its eval-mode one.
+    # A statement about the oracle alone, so it is made once, against the forward tolerance of the emulator run (for the retrieval
+    # logits: 6e-3 .. 1e-2 against 1.4e-4); the same move is 5 .. 13 x the wider tolerance of the GPU run, and is printed.
+    with torch.no_grad():
+        ref_eval = O.clipbert_forward(sd, oracle_batch(batch, head), cfg, head)
+
+    def moved(t):
+        return max(float(((ref[k].detach() - ref_eval[k]).abs() / (t["atol"] + t["rtol"] * ref_eval[k].abs())).max()) for k in outs if "loss" not in k)
+    print(f"[train vs eval oracle] {head}: largest move of an output = {moved(dict(rtol=1e-3, atol=1e-4)):.1f} x the emulator run's forward "
+          f"tolerance, {moved(ft):.1f} x this run's")
+    assert moved(dict(rtol=1e-3, atol=1e-4)) >= 10
+    assert moved(ft) >= 3                                        # (a wider tolerance of this run must not swallow the dropout signal)
+    out = model(to_dev(batch, hw.dev))
+    assert model.rt.forward_count == fwd_i + 1
+    for k in outs:
+        torch.testing.assert_close(out[k].cpu(), ref[k].detach(), **ft)
+    model.rt.bank.zero_grad()
+    loss_fn(out).backward()
+    assert_grads_match_oracle(hw, model, sdr)
+
+
+def test_two_train_forwards_one_backward_match_masked_oracle(hw):
+    """the timed step's pattern (n_clips forwards, then ONE backward): two training forwards of different inputs, the losses summed,
+    one backward -- each forward's backward must regenerate ITS masks (fwd_i and fwd_i + 1 in the oracle)."""
+    head = "retrieval"
+    cfg, sd, model = build(head, RETRIEVAL_CE, torch.float32, hw.dev)
+    model.train()
+    fwd_i = 7
+    model.rt.forward_count = fwd_i
+    sdr = oracle_leaves(sd, head)
+    cases = [train_case(cfg, head, 2, seed) for seed in (5, 6)]
+    assert not torch.equal(cases[0][0]["text_input_ids"], cases[1][0]["text_input_ids"])
+    ref_loss, refs = 0, []
+    for i, (batch, loss_fn, _) in enumerate(cases):
+        with O.dropout_masks(restated_masks(cfg, fwd_i + i, 0)):
+            refs.append(O.clipbert_forward(sdr, dict(batch), cfg, head))
+        ref_loss = ref_loss + loss_fn(refs[-1])
+    ref_loss.backward()
+    model.rt.bank.zero_grad()
+    loss = 0
+    for (batch, loss_fn, _), ref in zip(cases, refs):
+        out = model(to_dev(batch, hw.dev))
+        torch.testing.assert_close(out["logits"].cpu(), ref["logits"].detach(), **forward_tol(hw))
+        loss = loss + loss_fn(out)
+    assert model.rt.forward_count == fwd_i + 2
+    loss.backward()
+    assert_grads_match_oracle(hw, model, sdr)
+
+
+def test_train_mode_bf16_gradients_within_the_masked_oracle_yardstick(hw):
+    """bf16 model.train() (the benchmarked arithmetic, dropout on) against autograd through the masked fp32 oracle: one-minus-cosine of
+    the flat gradient and median per-tensor relative L2 (the figures of test_bench_step.py) held to PB.FACTOR x what the masked oracle
+    itself shows in its bf16-storage modes on the same batch with the same masks."""
+    head = "retrieval"
+    cfg, sd, model = build(head, RETRIEVAL_CE, torch.bfloat16, hw.dev)
+    model.train()
+    fwd_i, seed_word = 2, 99
+    model.rt.forward_count = fwd_i
+    model.rt.seed_dev.fill_(seed_word)
+    batch, loss_fn, _ = train_case(cfg, head, 2)
+    names = [name for name, p in model.named_parameters() if p.requires_grad]
+
+    def oracle_grads(mode):
+        sdr = oracle_leaves(sd, head)
+        with O.precision(mode), O.dropout_masks(restated_masks(cfg, fwd_i, seed_word)):
+            loss = loss_fn(O.clipbert_forward(sdr, dict(batch), cfg, head))
+        loss.backward()
+        return {n: (sdr[n].grad if sdr[n].grad is not None else torch.zeros_like(sdr[n])).double() for n in names}
+
+    def figures(grads, ref):
+        dot = n1 = n2 = 0.0
+        per = {}
+        for name, r in ref.items():
+            g = grads[name]
+            dot += float((g * r).sum()); n1 += float((g * g).sum()); n2 += float((r * r).sum())
+            if float(r.norm()) > 1e-8:
+                per[name] = float((g - r).norm() / r.norm())
+        return 1.0 - dot / (n1 ** 0.5 * n2 ** 0.5), float(np.median(list(per.values())))
+
+    ref = oracle_grads("fp32")
+    yard = [figures(oracle_grads(m), ref) for m in PB.MODES]
+    y_omc, y_med = max(y[0] for y in yard), max(y[1] for y in yard)
+    model.rt.bank.zero_grad()
+    loss_fn(model(to_dev(batch, hw.dev))).backward()
+    params = dict(model.named_parameters())
+    omc, med = figures({n: params[n].grad.detach().cpu().double() for n in names}, ref)
+    rec = dict(one_minus_cosine=omc, median_tensor_rel_l2=med, tensors=len(ref), yardstick_one_minus_cosine=y_omc, yardstick_median=y_med,
+               yardstick_modes=dict(zip(PB.MODES, yard)))
+    print(f"[train-mode bf16 vs masked oracle autograd, {hw.name}]", rec)
+    assert omc <= PB.FACTOR * y_omc, rec
+    assert med <= PB.FACTOR * y_med, rec
 
 
 def test_bf16_mode_close(hw):

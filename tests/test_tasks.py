@@ -195,8 +195,10 @@ def test_folded_clips_equal_clip_loop(hw, pool):
 
 def test_each_forward_draws_its_own_dropout_masks(hw):
     """nn.Dropout semantics: two training forwards of the same input differ (the per-forward counter is part of every
-    seed), while the backward of each forward regenerates exactly its own masks (gradient check by finite differences is
-    out of scope here: the mask agreement of the kernels is tested in test_kernels_misc)."""
+    seed).  That the backward of each forward regenerates exactly its own masks is checked where the gradients are: against the
+    oracle under the restated masks in test_model_small.py (test_train_mode_forward_backward_matches_masked_oracle_fp32,
+    test_two_train_forwards_one_backward_match_masked_oracle); every kernel's mask against the restatement in test_kernels_misc.py,
+    test_kernels_gemm8.py and test_gemm_skinny.py."""
     cfg, sd, model = build("retrieval", RET, torch.float32, hw.dev)
     model.train()
     vis = _frames(1, 2, 43)
