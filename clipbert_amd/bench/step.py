@@ -18,6 +18,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# the closures of one training step live in clipbert_amd.captured (the task loops capture the same `device_step`); bench.py and the
+# tests keep reaching them as bench_step.make_step
+from clipbert_amd.captured import make_step  # noqa: E402,F401
+
 BASE_CONFIG = dict(
     max_temporal_position_embeddings=100, backbone_channel_in_size=2048, max_grid_row_position_embeddings=100,
     max_grid_col_position_embeddings=100, attention_probs_dropout_prob=0.1, hidden_act="gelu", hidden_dropout_prob=0.1,
@@ -70,33 +74,3 @@ def build(videos=16, n_clips=2, frames=2, size=224, txt_len=32, repeat=2, pool="
                            forward_loss=fns.forward_loss, host_prepare=fns.host_prepare, device_step=fns.device_step, capture=capture, state=fns.state,
                            clips_per_step=videos * n_clips, dev=dev)
 
-
-def make_step(model, batch, tcfg, opt, sync, labels, counts, n_clips, frames, pool, fold=True):
-    """The closures of one training step on prepared objects -- bench.py's default path calls THIS (its `forward_loss`, `host_prepare`
-    and `device_step_single` are these functions), so tests/test_bench_step.py tests what is timed."""
-    from clipbert_amd import ops
-    from clipbert_amd import tasks
-    state = {"global_step": 0}
-    one = torch.ones((), dtype=torch.float32, device=labels.device)          # d(loss)/d(loss): persistent, so that backward() launches no fill
-
-    def forward_loss():
-        stack = tasks.forward_clips_stack(model, batch, n_clips, frames, fold=fold, cfg=tcfg)       # (n_clips, pairs, C) logits
-        return tasks.training_loss(model, stack, labels, counts, pool)                              # clip pooling (a20) + loss
-
-    def host_prepare():
-        """per-step host work of a real training loop: LR schedule onto the 8 groups, hyper-parameter upload"""
-        state["global_step"] += 1
-        tasks.set_learning_rates(opt, tcfg, state["global_step"])
-        opt.prepare_step(grad_scale=sync.grad_scale)
-
-    def device_step():
-        """everything a 1-GPU step enqueues (capturable)"""
-        opt.zero_grad(lazy=True)
-        model.rt.begin_step()
-        loss = forward_loss()
-        loss.backward(one)
-        ops.counter_add(model.rt.seed_dev)
-        opt.launch()
-        return loss
-
-    return SimpleNamespace(forward_loss=forward_loss, host_prepare=host_prepare, device_step=device_step, state=state, one=one)

@@ -497,6 +497,41 @@ __global__ __launch_bounds__(256) void zero_ranges_kernel(ZeroRanges zr) {
     if (tid < head) p[tid] = 0;
     if (tid < bytes - tail0) p[tail0 + tid] = 0;
 }
+// up to eight (dst, src, bytes) ranges in one launch (cb_copy_ranges): the grid is split over the ranges in proportion to their bytes
+// (blk0 = first block of each range), a block finds its range by walking blk0.  Per range, by the two pointers' misalignment:
+// equal mod 16 -> 16-byte loads / stores over the middle that is aligned for both; equal mod 4 -> dwords; otherwise bytes.  Head and
+// tail (< 16 bytes each) go byte-wise from the range's first block.
+struct CopyRanges { unsigned char* dst[8]; const unsigned char* src[8]; int64_t bytes[8]; int32_t blk0[9]; int32_t n; };
+template <typename V>
+__device__ inline void copy_range_body(unsigned char* d, const unsigned char* s, int64_t bytes, int64_t tid, int64_t stride) {
+    constexpr int64_t W = (int64_t)sizeof(V);
+    int64_t head = (int64_t)((W - (reinterpret_cast<uintptr_t>(d) & (W - 1))) & (W - 1));
+    if (head > bytes) head = bytes;
+    const int64_t nv = (bytes - head) / W;
+    V* q = reinterpret_cast<V*>(d + head);
+    const V* r = reinterpret_cast<const V*>(s + head);
+    int64_t i = tid;
+    for (; i + 3 * stride < nv; i += 4 * stride) {          // four loads in flight per thread before the first store
+        const V a = r[i], b = r[i + stride], c = r[i + 2 * stride], e = r[i + 3 * stride];
+        q[i] = a; q[i + stride] = b; q[i + 2 * stride] = c; q[i + 3 * stride] = e;
+    }
+    for (; i < nv; i += stride) q[i] = r[i];
+    const int64_t tail0 = head + nv * W;
+    if (tid < head) d[tid] = s[tid];
+    if (tid < bytes - tail0) d[tail0 + tid] = s[tail0 + tid];
+}
+__global__ __launch_bounds__(256) void copy_ranges_kernel(CopyRanges cr) {
+    int r = 0;
+    while (r + 1 < cr.n && (int)blockIdx.x >= cr.blk0[r + 1]) ++r;
+    unsigned char* d = cr.dst[r];
+    const unsigned char* s = cr.src[r];
+    const int64_t bytes = cr.bytes[r];
+    const int64_t tid = (int64_t)((int)blockIdx.x - cr.blk0[r]) * 256 + threadIdx.x, stride = (int64_t)(cr.blk0[r + 1] - cr.blk0[r]) * 256;
+    const uintptr_t diff = reinterpret_cast<uintptr_t>(d) ^ reinterpret_cast<uintptr_t>(s);
+    if ((diff & 15) == 0) copy_range_body<u32x4>(d, s, bytes, tid, stride);
+    else if ((diff & 3) == 0) copy_range_body<uint32_t>(d, s, bytes, tid, stride);
+    else for (int64_t i = tid; i < bytes; i += stride) d[i] = s[i];
+}
 }  // namespace
 
 extern "C" int cb_mean_fwd(const float* x, int64_t n, float* out, void* stream) {
@@ -536,6 +571,38 @@ extern "C" int cb_zero_ranges(void* const* ptrs, const int64_t* bytes, int32_t n
     if (blocks > 256 * 16) blocks = 256 * 16;
     hipLaunchKernelGGL(zero_ranges_kernel, dim3((unsigned)blocks, (unsigned)m), dim3(256), 0, cb_stream(stream), zr);
     return cb_launch_status("cb_zero_ranges");
+}
+extern "C" int cb_copy_ranges(void* const* dsts, const void* const* srcs, const int64_t* bytes, int32_t n, void* stream) {
+    CB_REQUIRE(n >= 0 && n <= 8 && (n == 0 || (dsts && srcs && bytes)), "cb_copy_ranges: 0..8 ranges");
+    CopyRanges cr{};
+    int m = 0;
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        CB_REQUIRE(bytes[i] >= 0 && (bytes[i] == 0 || (dsts[i] && srcs[i])), "cb_copy_ranges: bad range %d", i);
+        if (bytes[i] == 0) continue;
+        const uintptr_t d = reinterpret_cast<uintptr_t>(dsts[i]), s = reinterpret_cast<uintptr_t>(srcs[i]);
+        CB_REQUIRE(d + (uintptr_t)bytes[i] <= s || s + (uintptr_t)bytes[i] <= d, "cb_copy_ranges: range %d overlaps its own source", i);
+        cr.dst[m] = static_cast<unsigned char*>(dsts[i]); cr.src[m] = static_cast<const unsigned char*>(srcs[i]); cr.bytes[m] = bytes[i]; ++m;
+        total += bytes[i];
+    }
+    if (m == 0) return 0;
+    // memory-bound stream: ~4 16-byte moves per thread, at most 2048 blocks over all ranges (256 CUs x 8), grid-stride beyond that;
+    // every range gets its share of them by bytes and at least one
+    int64_t budget = (total + 256 * 4 * 16 - 1) / (256 * 4 * 16);
+    if (budget > 2048) budget = 2048;
+    int32_t at = 0;
+    for (int i = 0; i < m; ++i) {
+        int64_t nb = (int64_t)((double)budget * (double)cr.bytes[i] / (double)total);
+        const int64_t fits = (cr.bytes[i] + 256 * 16 - 1) / (256 * 16);          // blocks that would still have a 16-byte move each
+        if (nb > fits) nb = fits;
+        if (nb < 1) nb = 1;
+        cr.blk0[i] = at;
+        at += (int32_t)nb;
+    }
+    for (int i = m; i <= 8; ++i) cr.blk0[i] = at;
+    cr.n = m;
+    hipLaunchKernelGGL(copy_ranges_kernel, dim3((unsigned)at), dim3(256), 0, cb_stream(stream), cr);
+    return cb_launch_status("cb_copy_ranges");
 }
 extern "C" int cb_counter_add(int64_t* counter, int64_t inc, void* stream) {
     CB_REQUIRE(counter, "cb_counter_add: null counter");

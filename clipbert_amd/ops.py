@@ -473,6 +473,21 @@ def zero_many(tensors) -> None:
         _chk(_lib.get().cb_zero_ranges(ptrs, nbytes, len(chunk), _stream(chunk[0])), "cb_zero_ranges")
 
 
+def copy_ranges(pairs) -> None:
+    """dst[...] = src[...] for every (dst, src) pair of contiguous tensors with the same number of bytes, eight pairs per launch
+    (cb_copy_ranges) on the first destination's stream: a collated batch into the static buffers of a captured step"""
+    ps = [(d, s) for d, s in pairs if d.numel()]
+    for d, s in ps:
+        assert d.is_contiguous() and s.is_contiguous() and d.numel() * d.element_size() == s.numel() * s.element_size(), (d.shape, s.shape)
+        assert d.device == s.device, (d.device, s.device)
+    for i in range(0, len(ps), 8):
+        chunk = ps[i:i + 8]
+        dsts = (C.c_void_p * len(chunk))(*[_ptr(d) for d, _ in chunk])
+        srcs = (C.c_void_p * len(chunk))(*[_ptr(s) for _, s in chunk])
+        nbytes = (C.c_int64 * len(chunk))(*[d.numel() * d.element_size() for d, _ in chunk])
+        _chk(_lib.get().cb_copy_ranges(dsts, srcs, nbytes, len(chunk), _stream(chunk[0][0])), "cb_copy_ranges")
+
+
 def zeros(shape, dtype, device) -> torch.Tensor:
     return zero_(torch.empty(shape, dtype=dtype, device=device))
 

@@ -268,7 +268,8 @@ def validate_pretrain(model, val_loader, cfg, group=None) -> Dict[str, float]:
 
 
 def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=None, model_saver=None, restorer=None,
-                   total_n_examples: Optional[int] = None, fold_clips: bool = True, log_fn=None, overlap: bool = True, loss_fn=None) -> int:
+                   total_n_examples: Optional[int] = None, fold_clips: bool = True, log_fn=None, overlap: bool = True, loss_fn=None,
+                   capture=False) -> int:
     """The loop of start_training (run_video_retrieval.py:379-516 / run_video_qa.py:457-560) around train_step: infinite
     iteration over ``train_loader`` until cfg.num_train_steps optimizer steps, gradient accumulation, LR schedules with the
     multi-step epoch counter, validation + ``model_step_N.pt`` every cfg.valid_steps (and once at the end), restorer.step()
@@ -281,8 +282,25 @@ def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=N
     optimizer steps: the resumed global step is agreed on across the ranks (max), and when the ranks did not all restore the
     same step, the most advanced rank's parameters, AdamW moments and optimizer step count are broadcast before the first step.
 
-    ``loss_fn``: handed to every train_step (see there)."""
+    ``loss_fn``: handed to every train_step (see there).
+
+    ``capture``: False (default) = every step is the eager train_step.  True = the steps go through clipbert_amd.captured.CapturedStep:
+    a batch signature seen twice is captured as a hipGraph and replayed from then on, everything a graph must not freeze falls back to
+    train_step with a warning (see that module).  "dry" = its bookkeeping without graphs (tests), or pass a CapturedStep built by the
+    caller (``max_graphs``, ``pad_text_to``) on the SAME model, optimizer, loss_fn, fold_clips and sync (checked)."""
     from .data import InfiniteIterator
+    stepper = None
+    if capture:
+        from .captured import CapturedStep
+        if isinstance(capture, CapturedStep):
+            stepper = capture
+            differ = [n for n, v in (("model", model), ("optimizer", optimizer), ("loss_fn", loss_fn), ("sync", sync)) if getattr(stepper, n) is not v]
+            if bool(stepper.fold_clips) != bool(fold_clips):
+                differ.append("fold_clips")
+            if differ:                                      # (e.g. an object without the loop's multi-rank sync would capture a step without the exchange)
+                raise ValueError(f"start_training(capture=CapturedStep): the object was built with another {' / '.join(differ)} than the loop was called with")
+        else:
+            stepper = CapturedStep(model, optimizer, cfg, loss_fn=loss_fn, fold_clips=fold_clips, sync=sync, mode="dry" if capture == "dry" else "graph")
     if sync is not None and sync.world > 1 and overlap and model.rt is not None and model.rt.after_encoder_backward is None:
         sync.attach(model)
     acc = max(1, int(_get(cfg, "gradient_accumulation_steps", 1) or 1))
@@ -319,8 +337,11 @@ def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=N
         return global_step
     for micro, batch in enumerate(InfiniteIterator(train_loader)):
         n_epoch = int(1.0 * total_bsz * (global_step + 1) / total_n_examples) if total_n_examples else 0
-        loss = train_step(model, optimizer, batch, cfg, global_step, sync=sync, n_epoch=n_epoch, micro_step=micro, fold_clips=fold_clips,
-                          loss_fn=loss_fn)
+        if stepper is not None:
+            loss = stepper.step(batch, global_step, n_epoch=n_epoch, micro_step=micro)
+        else:
+            loss = train_step(model, optimizer, batch, cfg, global_step, sync=sync, n_epoch=n_epoch, micro_step=micro, fold_clips=fold_clips,
+                              loss_fn=loss_fn)
         if (micro + 1) % acc != 0:
             continue
         global_step += 1
@@ -342,7 +363,7 @@ def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=N
 # ---- retrieval inference (:628-734) ------------------------------------------------------------------------------------
 @torch.no_grad()
 def inference_retrieval_video(model, visual_inputs: torch.Tensor, text_input_ids: torch.Tensor, text_input_mask: torch.Tensor,
-                              cfg, cache_cnn: bool = True, max_pairs_per_pass: int = 256) -> List[float]:
+                              cfg, cache_cnn: bool = True, max_pairs_per_pass: int = 256, capture=None) -> List[float]:
     """Scores of ONE video (1, inference_n_clips*num_frm, 3, H, W) against all its candidate captions (:640-690).
 
     cache_cnn=True (row N1): the grid features of all clips are computed once, in one CNN batch, and every text
@@ -350,7 +371,19 @@ def inference_retrieval_video(model, visual_inputs: torch.Tensor, text_input_ids
     ``max_pairs_per_pass`` per encoder pass: measured on MI355X, an encoder batch whose activations outgrow the 256 MB
     Infinity Cache (1024 pairs = 42 k token rows: 258 MB per FFN activation) runs its GEMMs 3-5x slower per row than a
     batch of a few thousand rows).  cache_cnn=False is the reference's order of evaluation (full forward per clip per
-    mini-batch).  Both give the same scores."""
+    mini-batch).  Both give the same scores.
+
+    ``capture``: None / False (default) = eager encoder passes.  A clipbert_amd.captured.CapturedForward = the encoder passes replay from
+    its hipGraphs (one full and one remainder signature per video set; the CNN pass stays eager); True = the one kept on the model
+    (created on first use), so that the graphs outlive the call.  cache_cnn=True only."""
+    if capture:
+        from .captured import CapturedForward
+        if not cache_cnn:
+            raise ValueError("inference_retrieval_video(capture=...) replays the encoder passes over cached grid features: cache_cnn=True only")
+        if not isinstance(capture, CapturedForward):
+            if getattr(model, "_captured_forward", None) is None:
+                model._captured_forward = CapturedForward(model, mode="dry" if capture == "dry" else "graph")
+            capture = model._captured_forward
     n_clips, num_frm = _get(cfg, "inference_n_clips", 1), _get(cfg, "num_frm")
     pool, eval_bsz = _get(cfg, "score_agg_func", "mean"), _get(cfg, "inference_batch_size", 64)
     vis = visual_inputs.view(n_clips, num_frm, *visual_inputs.shape[2:])
@@ -365,10 +398,13 @@ def inference_retrieval_video(model, visual_inputs: torch.Tensor, text_input_ids
             per_clip = []
             for c0 in range(0, n_clips, cpp):
                 nc = min(cpp, n_clips - c0)
-                out = model.forward_from_grid(dict(visual_inputs=grid[c0:c0 + nc], text_input_ids=ids.repeat(nc, 1),
-                                                   text_input_mask=mask.repeat(nc, 1), labels=None,
-                                                   n_examples_list=[nb] * nc))
-                per_clip.extend(out["logits"].view(nc, nb, -1).unbind(0))
+                if capture:
+                    lg = capture.logits(grid[c0:c0 + nc], ids.repeat(nc, 1), mask.repeat(nc, 1), [nb] * nc)
+                else:
+                    lg = model.forward_from_grid(dict(visual_inputs=grid[c0:c0 + nc], text_input_ids=ids.repeat(nc, 1),
+                                                      text_input_mask=mask.repeat(nc, 1), labels=None,
+                                                      n_examples_list=[nb] * nc))["logits"]
+                per_clip.extend(lg.view(nc, nb, -1).unbind(0))
         else:
             per_clip = []
             for c in range(n_clips):
@@ -405,16 +441,17 @@ def gather_retrieval_rows(rows: List[Dict], group=None) -> List[Dict]:
 
 
 @torch.no_grad()
-def inference_retrieval(model, videos, cfg, gt_txt_id2vid_id: Optional[Dict] = None, group=None, cache_cnn: bool = True):
+def inference_retrieval(model, videos, cfg, gt_txt_id2vid_id: Optional[Dict] = None, group=None, cache_cnn: bool = True, capture=False):
     """inference_retrieval of the reference (:628-734) for the videos of THIS rank: ``videos`` yields dict(vid_id,
     visual_inputs (1, n_clips*num_frm, 3, H, W), text_input_ids, text_input_mask, caption_ids) -- one video against all its
     candidate captions.  Returns (rows of all ranks, metrics or None); videos are independent units, the only exchange is
-    the final gather of the score rows."""
+    the final gather of the score rows.  ``capture``: handed to every inference_retrieval_video (see there)."""
     was_training = model.training
     model.eval()
     rows: List[Dict] = []
     for b in videos:
-        scores = inference_retrieval_video(model, b["visual_inputs"], b["text_input_ids"], b["text_input_mask"], cfg, cache_cnn=cache_cnn)
+        scores = inference_retrieval_video(model, b["visual_inputs"], b["text_input_ids"], b["text_input_mask"], cfg, cache_cnn=cache_cnn,
+                                           capture=capture or None)
         rows.extend(dict(vid_id=b["vid_id"], txt_id=c, score=s) for c, s in zip(b["caption_ids"], scores))
     rows = gather_retrieval_rows(rows, group)
     metrics = eval_retrieval(rows, gt_txt_id2vid_id) if gt_txt_id2vid_id is not None else None

@@ -459,6 +459,14 @@ int cb_zero(void* p, int64_t bytes, void* stream);
 /* the same for up to FOUR ranges in one launch (round 6): zero_grad() of a step whose weight gradients are stored by their first writers
  * leaves three gaps of the flat gradient buffer + the norm slots to fill -- one launch instead of four.  ptrs / bytes: HOST arrays. */
 int cb_zero_ranges(void* const* ptrs, const int64_t* bytes, int32_t n, void* stream);
+/* dsts[i][0, bytes[i]) = srcs[i][0, bytes[i]) for up to EIGHT device ranges in one launch, any alignment (16-byte moves where the two
+ * pointers are misaligned alike, dwords or bytes where they are not); the grid is shared out over the ranges by their bytes.  Stages a
+ * collated batch (frames, ids, mask, labels, tables) into the static input buffers of a captured step: the reference's PrefetchLoader
+ * (src/datasets/dataloader.py:86-152: fresh .cuda(non_blocking=True) tensors per batch) hands every step NEW tensors, so it has
+ * no static buffers and nothing to stage; a replayed hipGraph reads fixed addresses.  dsts / srcs / bytes: HOST arrays (the ranges travel
+ * in the kernel arguments: no device-side table, capturable).  n = 0 and ranges of 0 bytes (null pointers allowed there) are no-ops.
+ * A range that overlaps its OWN source is refused; a destination that overlaps ANOTHER range's source or destination is undefined. */
+int cb_copy_ranges(void* const* dsts, const void* const* srcs, const int64_t* bytes, int32_t n, void* stream);
 int cb_sq_sum(const float* g, int64_t n, float* out_accum, void* stream);
 /* The same sum with a result that does not depend on the order in which workgroups retire (fixed grid of <= min(1024, ws_floats)
  * blocks -> `ws` partials -> one block adds them in index order): data-parallel ranks holding bit-identical all-reduced
@@ -515,7 +523,8 @@ const char* cb_last_error(void);
  * 8 = cb_resize_pack_u8 (raw-frame ingest: resize + pad + ImageNorm of native-resolution uint8 frames; nothing else changed);
  * 9 = cb_optim_step (CB_OPT_ADAM / CB_OPT_ADAMAX beside AdamW: the reference's other two cfg.optim choices; nothing else changed);
  * 10 = cb_resize_pack_yuv420 (the raw-frame ingest from I420 / NV12 planes; nothing else changed);
- * 11 = cb_mlm_select, cb_mlm_loss_fwd, cb_mlm_loss_bwd (the masked-LM head over the labelled rows only; nothing else changed) */
+ * 11 = cb_mlm_select, cb_mlm_loss_fwd, cb_mlm_loss_bwd (the masked-LM head over the labelled rows only; nothing else changed);
+ * 12 = cb_copy_ranges (batch staging for captured task loops; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
