@@ -136,6 +136,9 @@ __device__ __forceinline__ float apply_act(int act, float v) {
         default: return v;
     }
 }
+// the sigmoid of the head losses and retrieval scores (misc.hip) and of the sparse-answer VQA loss (vqa.hip): one expression, so that the
+// dense and the fused BCE gradients agree
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
 // ---- stateless dropout mask ------------------------------------------------------------------------
 // One 64-bit hash (splitmix64 finaliser) decides FOUR consecutive elements, 16 bits each (the 64-bit multiplies are the

@@ -259,8 +259,6 @@ inline unsigned nblk(int64_t n, int per) { return (unsigned)((n + per - 1) / per
 
 
 // ---- element-wise head losses and retrieval scores (fp32 logits; a handful of values per step, but part of the path: a16 / a18) ----
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
-
 // kind 0 / 1: one thread per element; kind 2 (sigmoid margin ranking): one thread per row of `group` logits (first = the positive)
 __global__ void __launch_bounds__(256) head_loss_kernel(int kind, const float* x, const float* y, float* loss, const float* dloss, float* dx,
                                                         int64_t n, int group, float margin) {

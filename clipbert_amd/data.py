@@ -214,6 +214,34 @@ def collate_yuv_frames(videos: Sequence, max_img_size: int, layout: str = "i420"
     return RawFrames(torch.cat(chunks), table, max_img_size, pixfmt=layout, matrix=matrix)
 
 
+# ---- VQA targets kept sparse (host lists -> two small tables) ----------------------------------------------------------------
+def vqa_sparse_targets(answers: Sequence[Dict[str, float]], ans2label: Dict[str, int], max_answers: int = 10):
+    """The soft targets of ``len(answers)`` questions -- each a dict answer -> score, as the annotations carry them -- as fixed-shape
+    tables for cb_vqa_loss_fwd / _bwd: (ids int32 (n, K), scores fp32 (n, K)), K = max_answers, slots in the dict's order, padding id -1
+    with score 0.  What ClipBertVQADataset._get_vqa_targets (src/datasets/dataset_vqa.py:57-72) scatters into num_labels zeros per
+    question; an answer missing from ``ans2label`` raises KeyError as its line 68 does, more than ``max_answers`` answers ValueError."""
+    n, k = len(answers), int(max_answers)
+    ids = torch.full((n, k), -1, dtype=torch.int32)
+    scores = torch.zeros((n, k), dtype=torch.float32)
+    for i, ans2score in enumerate(answers):
+        if len(ans2score) > k:
+            raise ValueError(f"question {i} has {len(ans2score)} answers, the tables hold max_answers = {k}")
+        for j, (ans, score) in enumerate(ans2score.items()):
+            ids[i, j] = ans2label[ans]
+            scores[i, j] = score
+    return ids, scores
+
+
+def vqa_dense_targets(ids: torch.Tensor, scores: torch.Tensor, num_labels: int) -> torch.Tensor:
+    """the inverse of vqa_sparse_targets: fp32 (n, num_labels) targets, the scatter of _get_vqa_targets (padding slots -- id < 0 or
+    >= num_labels -- dropped); the reference's batch format, for the dense ``labels`` path and the tests"""
+    ids, scores = ids.cpu().long(), scores.cpu().float()
+    valid = (ids >= 0) & (ids < num_labels)
+    dense = torch.zeros(ids.shape[0], num_labels + 1, dtype=torch.float32)
+    dense.scatter_(1, torch.where(valid, ids, torch.full_like(ids, num_labels)), torch.where(valid, scores, torch.zeros_like(scores)))
+    return dense[:, :num_labels].contiguous()
+
+
 class InfiniteIterator:
     """iterate an iterable object infinitely (src/datasets/dataloader.py:155-175)"""
     def __init__(self, iterable):

@@ -143,6 +143,43 @@ class _MlmDecoderLossFn(torch.autograd.Function):
         return None, dh, None, None, None, None
 
 
+class _VqaHeadLossFn(torch.autograd.Function):
+    """Last classifier Linear (modeling.py:338-343) + the BCE-with-logits loss of the VQA head on SPARSE answers (modeling.py:310-316,
+    372-374; the targets of dataset_vqa.py:57-72 as (pairs, K) id / score tables): fp32 logits (pairs, C) -> per-pair loss (pairs,) = the
+    row sums of the reference's (pairs, C) loss, with the arg-max and its VQA score (run_vqa.py:188, dataset_vqa.py:93-97) from the same
+    pass.  ONE node for the two stages, for the reason _MlmDecoderLossFn gives: cb_vqa_loss_bwd writes the gradient once, in the compute
+    dtype, as the A operand of the two backward GEMMs."""
+    @staticmethod
+    def forward(ctx, anchor, h, rt, weight, bias, ans_ids, ans_scores):
+        n, k = weight.shape
+        h2 = h.reshape(-1, k)
+        m = h2.shape[0]
+        logits = torch.empty(m, (n + 3) // 4 * 4, dtype=torch.float32, device=h.device)[:, :n]
+        ops.gemm(h2, rt.bank.compute(weight), m, n, k, out=logits, shift=bias, act=ACT_NONE)
+        loss, pred, score = ops.vqa_loss_fwd(logits, ans_ids, ans_scores)
+        ctx.rt, ctx.weight, ctx.bias, ctx.saved, ctx.h_shape = rt, weight, bias, (h2, logits, ans_ids, ans_scores), h.shape
+        ctx.mark_non_differentiable(logits, pred, score)
+        ctx.set_materialize_grads(False)                 # (no zero matrix for the logits' absent gradient)
+        return loss, logits, pred, score
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits, _dpred, _dscore):
+        if dloss is None:
+            return (None,) * 7
+        rt, weight, bias = ctx.rt, ctx.weight, ctx.bias
+        h2, logits, ans_ids, ans_scores = ctx.saved
+        bank = rt.bank
+        n, k = weight.shape
+        m = h2.shape[0]
+        g = ops.vqa_loss_bwd(logits, ans_ids, ans_scores, dloss.contiguous(), rt.dtype)
+        gb = _linear_wgrad(g, h2, m, n, k, bank.grad_image(weight), bank.grad_image(bias) if bias is not None else None, defer_bias=True)
+        dh = torch.empty(h2.shape, dtype=rt.dtype, device=h2.device)
+        ops.gemm(g, bank.compute(weight), m, k, n, out=dh, lda=g.stride(0), b_mode=KROW)
+        if gb is not None:
+            ops.colsum(g, gb, m, n)
+        return None, dh.view(ctx.h_shape), None, None, None, None, None
+
+
 class _HeadLossFn(torch.autograd.Function):
     """Element-wise head losses of the reference through cb_head_loss (reduction "none"): MSE (num_labels == 1), BCE with logits (VQA-style
     soft targets), sigmoid margin ranking of the retrieval head -- src/modeling/modeling.py:359-381, 431-446, 567-575."""
@@ -250,6 +287,27 @@ class ClipBertForSequenceClassification(_ClipBertHead):
     def __init__(self, config):
         super().__init__(config)
         self.classifier = _make_mlp(self.config.hidden_size, self.config.num_labels)
+
+    def forward(self, text_input_ids, visual_inputs, text_input_mask, labels=None, src_row=None, text_repeat=1, answer_ids=None,
+                answer_scores=None):
+        """``answer_ids`` int32 / ``answer_scores`` fp32 (pairs, K) (data.vqa_sparse_targets: padding id -1): the VQA targets kept sparse.
+        The last classifier Linear and the loss then run as one node and the call returns dict(logits, loss (pairs,): the ROW SUMS of the
+        dense path's (pairs, num_labels) loss, pred (pairs,) int64: the arg-max, pred_score (pairs,) fp32: its VQA soft accuracy).
+        Without them: the dense ``labels`` path, unchanged."""
+        if answer_ids is None and answer_scores is None:
+            return super().forward(text_input_ids, visual_inputs, text_input_mask, labels, src_row, text_repeat)
+        if answer_ids is None or answer_scores is None:
+            raise ValueError("answer_ids and answer_scores come together")
+        if labels is not None:
+            raise ValueError("sparse answers (answer_ids / answer_scores) and dense labels exclude each other")
+        if self.config.loss_type != "bce" or self.config.num_labels <= 1:
+            raise ValueError(f"sparse answers need loss_type 'bce' and num_labels > 1, not {self.config.loss_type!r} / {self.config.num_labels}")
+        _, pooled = self.bert(text_input_ids, visual_inputs, text_input_mask, src_row, pooled_dropout=True, text_repeat=text_repeat)
+        rt, (fc1, _, fc2) = self.rt, self.classifier
+        h = _LinearFn.apply(rt.anchor, pooled, rt, fc1.weight, fc1.bias, ACT_RELU, False, None)
+        loss, logits, pred, score = _VqaHeadLossFn.apply(rt.anchor, h, rt, fc2.weight, fc2.bias, answer_ids.to(torch.int32).contiguous(),
+                                                         answer_scores.to(torch.float32).contiguous())
+        return dict(logits=logits, loss=loss, pred=pred, pred_score=score)
 
 
 class _EluBnFn(torch.autograd.Function):

@@ -582,6 +582,41 @@ def mlm_loss_bwd(logits: torch.Tensor, lse: torch.Tensor, sel: MlmSelection, dlo
     return store[:, :v]
 
 
+def _vqa_args(logits, ans_ids, ans_scores):
+    rows, c = logits.shape
+    assert logits.dtype == torch.float32 and (logits.stride(1) == 1 or c == 1)
+    assert ans_ids.dtype == torch.int32 and ans_scores.dtype == torch.float32 and ans_ids.dim() == 2 and ans_ids.shape == ans_scores.shape
+    assert ans_ids.shape[0] == rows and ans_ids.is_contiguous() and ans_scores.is_contiguous(), (ans_ids.shape, rows)
+    return rows, c, logits.stride(0) if rows > 1 else max(logits.stride(0), c), ans_ids.shape[1]
+
+
+def vqa_loss_fwd(logits: torch.Tensor, ans_ids: torch.Tensor, ans_scores: torch.Tensor):
+    """cb_vqa_loss_fwd on fp32 logits (rows, C) (row stride may exceed C) and the (rows, K) answer tables (int32 ids, padding < 0 or >= C;
+    fp32 scores) -> (loss_rows fp32 (rows,): the row sums of the BCE-with-logits loss; pred_rows int64 (rows,): the arg-max;
+    pred_score fp32 (rows,): the VQA soft accuracy of the arg-max)."""
+    rows, c, ld, k = _vqa_args(logits, ans_ids, ans_scores)
+    dev = logits.device
+    loss = torch.empty(rows, dtype=torch.float32, device=dev)
+    pred = torch.empty(rows, dtype=torch.int64, device=dev)
+    score = torch.empty(rows, dtype=torch.float32, device=dev)
+    _chk(_lib.get().cb_vqa_loss_fwd(_ptr(logits), ld, _ptr(ans_ids), _ptr(ans_scores), k, rows, c, _ptr(loss), _ptr(pred), _ptr(score),
+                                    _stream(logits)), "cb_vqa_loss_fwd")
+    return loss, pred, score
+
+
+def vqa_loss_bwd(logits: torch.Tensor, ans_ids: torch.Tensor, ans_scores: torch.Tensor, dloss_rows: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """cb_vqa_loss_bwd: the (rows, C) view of a new (rows, ldd) ``dtype`` buffer (ldd = C rounded up to 16 bytes) holding
+    d(sum_r dloss_rows[r] loss_rows[r])/d(logits) -- the A operand of the classifier's two backward GEMMs."""
+    rows, c, ld, k = _vqa_args(logits, ans_ids, ans_scores)
+    assert dloss_rows.dtype == torch.float32 and dloss_rows.is_contiguous() and dloss_rows.numel() == rows
+    per16 = 8 if dtype == torch.bfloat16 else 4
+    ldd = (c + per16 - 1) // per16 * per16
+    store = torch.empty(rows, ldd, dtype=dtype, device=logits.device)
+    _chk(_lib.get().cb_vqa_loss_bwd(dtype_code(dtype), _ptr(logits), ld, _ptr(ans_ids), _ptr(ans_scores), k, _ptr(dloss_rows), _ptr(store),
+                                    ldd, rows, c, _stream(logits)), "cb_vqa_loss_bwd")
+    return store[:, :c]
+
+
 LOSS_MSE, LOSS_BCE, LOSS_RANK = 0, 1, 2
 
 

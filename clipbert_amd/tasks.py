@@ -21,7 +21,7 @@ def _get(cfg, name, default=None):
 
 
 # ---- training (run_video_retrieval.py:380-494) ------------------------------------------------------------------------
-_SKIP_KEYS = ("visual_inputs", "caption_ids", "vid_id", "question_ids", "n_examples_list")
+_SKIP_KEYS = ("visual_inputs", "caption_ids", "vid_id", "question_ids", "n_examples_list", "answer_types")
 
 
 def _pair_counts(cfg, n_examples_list):
@@ -125,6 +125,27 @@ def pretrain_loss(model, batch: Dict, cfg) -> torch.Tensor:
     if not parts:
         raise ValueError("pretrain_loss: neither cfg.use_mlm nor cfg.use_itm leaves a loss (or the batch carries no labels for it)")
     return parts[0] if len(parts) == 1 else parts[0] + parts[1]
+
+
+def _vqa_forward(model, batch: Dict) -> Dict:
+    """forward_step of src/tasks/run_vqa.py:164-169: the batch without its question ids (and without the answer types the metric reads)"""
+    mini = {k: v for k, v in batch.items() if k not in ("question_ids", "answer_types")}
+    mini["n_examples_list"] = list(mini["n_examples_list"])
+    return model(mini)
+
+
+def vqa_loss(model, batch: Dict, cfg) -> torch.Tensor:
+    """The loss of the image-VQA loop (run_vqa.py:353-356): loss.mean() * num_labels of the (pairs, num_labels) BCE-with-logits loss.  A
+    ``loss_fn`` for train_step / start_training / CapturedStep.  With ``answer_ids`` / ``answer_scores`` in the batch (data.
+    vqa_sparse_targets) the head returns the row sums and this is their mean -- the same number; with the reference's dense ``labels`` it
+    is the element-wise path times num_labels."""
+    sparse = batch.get("answer_ids") is not None
+    if not sparse and batch.get("labels") is None:
+        raise ValueError("vqa_loss: the batch carries neither answer_ids / answer_scores nor labels")
+    out = _vqa_forward(model, batch)
+    if sparse:
+        return clips.mean_loss(out["loss"])
+    return clips.mean_loss(out["loss"].reshape(-1)) * float(out["loss"].shape[-1])
 
 
 def train_step(model, optimizer, batch: Dict, cfg, global_step: int, sync=None, n_epoch: int = 0, micro_step: int = 0,
@@ -265,6 +286,85 @@ def validate_pretrain(model, val_loader, cfg, group=None) -> Dict[str, float]:
     if n_ex != 0:
         log.update({"valid/itm_loss": float(itm_loss / n_ex), "valid/itm_acc": float(n_ex_ok / n_ex)})
     return log
+
+
+VQA_ANSWER_TYPES = ("yes/no", "number", "other")          # answer_type2idx of ClipBertVQADataset.evaluate_vqa (dataset_vqa.py:88)
+
+
+def vqa_pred_scores(pred_ids: Sequence[int], ans_ids, ans_scores) -> np.ndarray:
+    """float64 (n,): the VQA soft accuracy of each predicted answer id against the question's (n, K) answer tables (dataset_vqa.py:93-97:
+    the annotated score of the predicted answer, 0 when it is none of them) -- on the host what cb_vqa_loss_fwd's pred_score is on the
+    device"""
+    ids = np.asarray(torch.as_tensor(ans_ids).cpu(), dtype=np.int64)
+    sc = np.asarray(torch.as_tensor(ans_scores).cpu(), dtype=np.float64)
+    pred = np.asarray(list(pred_ids), dtype=np.int64).reshape(-1, 1)
+    return (sc * ((ids == pred) & (ids >= 0))).sum(axis=1)
+
+
+def vqa_score_sums(scores, answer_types: Optional[Sequence[str]] = None) -> Dict[str, list]:
+    """[sum of scores, count] in float64 / int for "overall" and, with ``answer_types`` (one of VQA_ANSWER_TYPES per question), for each
+    type: what validate_vqa accumulates per batch and sums over the ranks"""
+    scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+    sums = {"overall": [float(scores.sum()), int(scores.size)]}
+    if answer_types is not None:
+        types = np.asarray(list(answer_types))
+        assert types.shape == scores.shape, (types.shape, scores.shape)
+        unknown = set(types.tolist()) - set(VQA_ANSWER_TYPES)
+        if unknown:
+            raise KeyError(f"unknown answer type(s) {sorted(unknown)}: expected one of {VQA_ANSWER_TYPES}")
+        for t in VQA_ANSWER_TYPES:
+            sel = scores[types == t]
+            sums[t] = [float(sel.sum()), int(sel.size)]
+    return sums
+
+
+def vqa_metrics(sums: Dict[str, list]) -> Dict[str, float]:
+    """{"overall_acc", "yes/no_acc", "number_acc", "other_acc"} (those whose count is not 0) as the reference reports them:
+    get_rounded_percentage of the mean score (dataset_vqa.py:99-107, run_vqa.py:220-242)"""
+    return {f"{k}_acc": round(100 * (s / n), 2) for k, (s, n) in sums.items() if n}
+
+
+def evaluate_vqa(pred_ids: Sequence[int], answer_types: Optional[Sequence[str]], ans_ids, ans_scores) -> Dict[str, float]:
+    """ClipBertVQADataset.evaluate_vqa (dataset_vqa.py:74-112) on answer ids and the sparse tables instead of strings and the dataset's
+    qid2data, in rounded percent"""
+    return vqa_metrics(vqa_score_sums(vqa_pred_scores(pred_ids, ans_ids, ans_scores), answer_types))
+
+
+@torch.no_grad()
+def validate_vqa(model, val_loader, cfg, label2ans=None, group=None):
+    """validate of src/tasks/run_vqa.py:172-257 -> (rows, log).  rows: dict(question_id, answer) per question, answer =
+    label2ans[predicted id] (the id itself without ``label2ans``).  log["valid/loss"] = the summed loss / the number of questions.  Batches
+    with ``answer_ids`` / ``answer_scores`` take loss, arg-max and the score of the arg-max from the fused head and also yield
+    valid/overall_acc and -- where they carry an ``answer_types`` list -- valid/yes/no_acc, valid/number_acc, valid/other_acc, each
+    round(100 * x, 2) (get_rounded_percentage); dense ``labels`` give the loss only; batches without answers (test sets) give the rows
+    from logits.max(dim=-1)[1] and no scores.  Score sums and counts are kept on the host in float64 and summed over the ranks: exact
+    sums where the reference re-weights per-rank means (:223-242), the same value up to rounding."""
+    was_training = model.training
+    model.eval()
+    rows, loss, n_ex = [], 0.0, 0
+    sums = {k: [0.0, 0] for k in ("overall",) + VQA_ANSWER_TYPES}
+    for batch in val_loader:
+        out = _vqa_forward(model, batch)
+        n = out["logits"].shape[0]
+        qids = batch.get("question_ids", list(range(n_ex, n_ex + n)))
+        if torch.is_tensor(out["loss"]):
+            loss += float(out["loss"].sum().item())
+        n_ex += n
+        if "pred" in out:
+            pred = out["pred"].tolist()
+            part = vqa_score_sums(out["pred_score"].double().cpu().numpy(), batch.get("answer_types"))
+            for k, (s, c) in part.items():
+                sums[k][0] += s
+                sums[k][1] += c
+        else:
+            pred = out["logits"].max(dim=-1)[1].tolist()
+        rows.extend(dict(question_id=q, answer=label2ans[p] if label2ans is not None else p) for q, p in zip(qids, pred))
+    loss, n_ex = _all_sum(loss, group), _all_sum(n_ex, group)
+    sums = {k: [_all_sum(s, group), _all_sum(c, group)] for k, (s, c) in sums.items()}
+    model.train(was_training)
+    log = {"valid/loss": float(loss / max(n_ex, 1))}
+    log.update({f"valid/{k}": v for k, v in vqa_metrics(sums).items()})
+    return rows, log
 
 
 def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=None, model_saver=None, restorer=None,

@@ -396,6 +396,27 @@ int cb_mlm_loss_fwd(const float* logits, int64_t ld, const int32_t* slot_row, co
 int cb_mlm_loss_bwd(int32_t dtype, const float* logits, int64_t ld, const float* lse, const int32_t* slot_row, const int64_t* slot_label,
                     int64_t ignore_index, const float* dloss_rows, void* dlogits, int64_t ldd, int32_t cap, int32_t V, void* stream);
 
+/* ---- image-VQA head over SPARSE answers -----------------------------------------------------------------------------------------------
+ * The VQA targets are at most ten (answer, score) pairs per question that ClipBertVQADataset._get_vqa_targets
+ * (src/datasets/dataset_vqa.py:57-72) scatters into num_labels = 3129 zeros; here they stay sparse: ans_ids int32 / ans_scores fp32,
+ * contiguous (rows, K), 1 <= K <= 32.  A slot whose id is < 0 or >= C is padding and its score is never used; valid slots of one row that
+ * name the same id add up.  logits fp32 (rows, C), row stride ld >= C (the columns C..ld-1 are never read).  Per row r, ONE pass:
+ * loss_rows[r] = sum_c (max(x, 0) + log1p(exp(-|x|))) - sum_{valid k} s_k x[a_k]: the row sum of instance_bce_with_logits(reduction=
+ * "none") (src/modeling/modeling.py:310-316, 372-374) -- its mean over the rows is the runner's loss.mean() * num_labels
+ * (src/tasks/run_vqa.py:355-356), its sum the validation's loss.sum() (:185);
+ * pred_rows[r] = argmax_c x[r, c], the lowest index among equals: logits.max(dim=-1)[1] (:188);
+ * pred_score[r] = sum_{valid k} s_k [a_k == pred_rows[r]]: the VQA soft accuracy of the predicted answer (dataset_vqa.py:93-97), 0 when
+ * the prediction is none of the answers.  rows = 0 launches nothing. */
+int cb_vqa_loss_fwd(const float* logits, int64_t ld, const int32_t* ans_ids, const float* ans_scores, int32_t K, int32_t rows, int32_t C,
+                    float* loss_rows, int64_t* pred_rows, float* pred_score, void* stream);
+/* dlogits[r, c] = dloss_rows[r] * (sigmoid(x[r, c]) - t[r, c]), t = the targets the slots describe (never materialised) -- the autograd
+ * backward of modeling.py:310-316 summed over the row -- in `dtype` (CB_F32 | CB_BF16; fp32 arithmetic, rounded once) into a (rows, ldd)
+ * buffer, ldd >= C: the A operand of the classifier's data- and weight-gradient GEMMs (the last Linear of modeling.py:338-343 under
+ * autograd) as it is -- no fp32 gradient matrix, no cast.  The columns C..ldd-1 receive zeros (they enter the weight gradient's
+ * reduction). */
+int cb_vqa_loss_bwd(int32_t dtype, const float* logits, int64_t ld, const int32_t* ans_ids, const float* ans_scores, int32_t K,
+                    const float* dloss_rows, void* dlogits, int64_t ldd, int32_t rows, int32_t C, void* stream);
+
 /* Column sums: out[n] (+)= sum_m g[m,n]  (bias gradients).  fp32 atomics into out. */
 int cb_colsum(int32_t dtype, const void* g, int64_t ldg, float* out, int64_t M, int32_t N, void* stream);
 
@@ -524,7 +545,8 @@ const char* cb_last_error(void);
  * 9 = cb_optim_step (CB_OPT_ADAM / CB_OPT_ADAMAX beside AdamW: the reference's other two cfg.optim choices; nothing else changed);
  * 10 = cb_resize_pack_yuv420 (the raw-frame ingest from I420 / NV12 planes; nothing else changed);
  * 11 = cb_mlm_select, cb_mlm_loss_fwd, cb_mlm_loss_bwd (the masked-LM head over the labelled rows only; nothing else changed);
- * 12 = cb_copy_ranges (batch staging for captured task loops; nothing else changed) */
+ * 12 = cb_copy_ranges (batch staging for captured task loops; nothing else changed);
+ * 13 = cb_vqa_loss_fwd, cb_vqa_loss_bwd (the image-VQA head over sparse answers; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
