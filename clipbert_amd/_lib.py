@@ -35,7 +35,7 @@ class GemmDesc(C.Structure):
         ("xcd_order", i32), ("a_bytes", i64), ("b_bytes", i64), ("gelu_grad_pre", vp), ("ld_gelu", i64), ("a_rowsum", vp),
         ("batch", i32), ("relu_bwd", i32), ("batch_stride_a", i64), ("batch_stride_b", i64), ("batch_stride_c", i64),
         ("batch_stride_rowsum", i64), ("post_scale", vp), ("post_scale2", vp), ("splitk_ws", vp), ("splitk_ws_bytes", i64),
-        ("sq_slots", vp), ("sq_slots_n", i64),
+        ("sq_slots", vp), ("sq_slots_n", i64), ("res_rowmap", vp), ("res_rows", i32), ("dgrad_s2", i32),
     ]
 
 

@@ -189,6 +189,18 @@ int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
     p.M = d->M; p.N = d->N; p.K = d->K;
     p.a_mode = d->a_mode; p.b_mode = d->b_mode;
     p.R = d->R > 0 ? d->R : 1; p.S = d->S > 0 ? d->S : 1; p.Ct = d->Cin; p.H = d->H; p.W = d->W; p.flip = d->flip_taps;
+    p.res_rowmap = d->res_rowmap;
+    if (d->res_rowmap) {
+        CB_REQUIRE(d->residual && d->res_rows > 0 && p.batch == 1 && (int64_t)d->res_rows * d->ldr * esz < 0x7fffffffll,
+                   "cb_gemm: res_rowmap needs a residual of res_rows > 0 rows that ends below 2 GiB, and one problem per launch");
+    }
+    if (d->dgrad_s2) {
+        CB_REQUIRE(d->a_mode == CB_ROWK_GATHER && d->b_mode == CB_KROW_TAPS && d->R == 3 && d->S == 3 && d->M % 4 == 0 && d->c_rowmap &&
+                   d->ldb == (int64_t)9 * d->N && p.batch == 1 && d->split_k <= 1 && !d->zero_fill_pitch,
+                   "cb_gemm: dgrad_s2 needs A CB_ROWK_GATHER, B CB_KROW_TAPS with R = S = 3 and ldb = 9 N, M a multiple of 4, c_rowmap, no batch / K split / zero fill");
+        p.cls_rows = d->M / 4;
+        p.flip = 0;                                   // (each workgroup sets its class's tap base: dgrad_s2_class)
+    }
     CB_REQUIRE(d->accumulate >= 0 && d->accumulate <= 2 && (d->accumulate != 2 || d->dtype == CB_BF16), "cb_gemm: bad accumulate %d (2 = first writer: bf16 problems)", d->accumulate);
     p.c_f32 = d->c_f32; p.accumulate = d->accumulate == 1; p.split_k = d->split_k > 0 ? d->split_k : 1;
     p.act = d->act; p.relu_after = d->relu_after;
@@ -199,7 +211,8 @@ int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
     {   // write-through (sc1) bf16 epilogue stores (round 5, profiles/r05b_bench_ab_wt.txt: -0.10 ... -0.14 ms per step, four alternating runs):
         // the output leaves for the memory side while the other workgroups still compute, instead of sitting dirty in the XCD's L2 until
         // the end-of-kernel release writes it back in one burst.  CB_GEMM_WT=0 restores plain stores; =3 adds nt on the second output.
-        const bool ok = d->dtype == CB_BF16 && !d->c_f32 && (int64_t)d->M * (d->ldc > d->ldc2 ? d->ldc : d->ldc2) * 2 * (p.batch) < 0xffffffffll && !d->c_rowmap;
+        const bool ok = d->dtype == CB_BF16 && !d->c_f32 && (int64_t)d->M * (d->ldc > d->ldc2 ? d->ldc : d->ldc2) * 2 * (p.batch) < 0xffffffffll &&
+                        (!d->c_rowmap || d->dgrad_s2);        // (dgrad_s2's row map is a permutation of the M output rows: the same extent)
         p.wt = ok ? switches().wt : 0;
     }
     {   // specialised epilogue (FAST_EPI_COMBOS in gemm_impl.h): the call's option combination, if it is one of the listed ones and the
@@ -221,11 +234,11 @@ int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
         }
         const bool plain = !wg_store && !fe_off && p.wt == 1 && p.batch == 1 && d->accumulate != 1 && p.alpha == 1.f && !d->zero_fill_pitch && !d->a_rowsum &&
                            d->N % 8 == 0 && d->ldc % 8 == 0 && aligned16(d->C) && (!d->shift || aligned16(d->shift)) && (!d->scale || aligned16(d->scale)) &&
-                           rows_ok(d->residual, d->ldr) && rows_ok(d->mask, d->ldm) && rows_ok(d->gelu_grad_pre, d->ld_gelu) &&
+                           (d->res_rowmap ? (d->ldr % 8 == 0 && aligned16(d->residual)) : rows_ok(d->residual, d->ldr)) && rows_ok(d->mask, d->ldm) && rows_ok(d->gelu_grad_pre, d->ld_gelu) &&
                            !(d->mask && d->gelu_grad_pre);
         if (plain && d->relu_bwd) {                                          // (validated above: mask, no scale / shift / act / dropout / relu_after)
             const bool ok = d->C2 && d->post_scale && d->ldc2 % 8 == 0 && aligned16(d->C2) && (int64_t)d->M * d->ldc2 * 2 < 0xffffffffll;
-            const int flags = EF_RBWD | (d->residual ? EF_RES : 0) | (d->post_scale2 ? EF_PS2 : 0);
+            const int flags = EF_RBWD | (d->residual ? EF_RES : 0) | (d->post_scale2 ? EF_PS2 : 0) | (d->res_rowmap ? EF_RMAP : 0) | (d->dgrad_s2 ? EF_CMAP : 0);
             if (ok)
                 for (int i = 1; i < FAST_EPI_N; ++i)
                     if (FAST_EPI_COMBOS[i] == flags) { p.fast_epi = i; break; }
@@ -244,8 +257,10 @@ int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
             if (d->gelu_grad_pre && !(flags & EF_MULAUX)) ok = false;        // (GELU' evaluated from the pre-activation: generic path)
             if (d->dropout_p > 0.f) flags |= EF_DROP;
             if (d->residual) flags |= EF_RES;
+            if (d->res_rowmap) flags |= EF_RMAP;
             if (d->relu_after) flags |= EF_RELU_AFTER;
             if (d->mask) flags |= EF_MASK;
+            if (d->dgrad_s2) flags |= EF_CMAP;
             if (ok)
                 for (int i = 1; i < FAST_EPI_N; ++i)
                     if (FAST_EPI_COMBOS[i] == flags) { p.fast_epi = i; break; }
@@ -415,7 +430,7 @@ extern "C" int cb_gemm_workspace_bytes(const cb_gemm_desc* d, int64_t* bytes) {
 namespace {
 // kernel class of a prepared problem for the grouped kernels, or -1: launched on its own
 int group_class(const cb_gemm_desc* d, const Prepared& pr) {
-    if (!pr.fast || d->zero_fill_pitch || d->tile >= 5 || d->tile == 1 || d->tile == 3) return -1;
+    if (!pr.fast || d->zero_fill_pitch || d->tile >= 5 || d->tile == 1 || d->tile == 3 || d->res_rowmap || d->dgrad_s2) return -1;
     if (d->batch > 1 || d->a_rowsum) {
         // strided batches and bias row sums: the unsplit bf16 weight-gradient form on the 128x128 two-per-CU tile only (GC_WGRAD_RS: the
         // encoder's four kinds of 12-layer weight gradients share one grid -- their last waves of tiles fill each other's)

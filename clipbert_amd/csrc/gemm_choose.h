@@ -109,7 +109,8 @@ ModelPick model_pick(const cb_gemm_desc* d, const Prepared& pr, bool can8, int64
     const int form = model_form(pr.form), split_caller = p.split_k;
     const bool taps = pr.taps > 1;
     const int c_esz = d->c_f32 ? 4 : 2;
-    const int64_t M = d->M, N = d->N, K = d->K, batch = p.batch;
+    // (dgrad_s2: the four classes reduce over 1, 2, 2 and 4 of the nine taps -- a row's mean reduction is K / 4)
+    const int64_t M = d->M, N = d->N, K = d->dgrad_s2 ? d->K / 4 : d->K, batch = p.batch;
     ModelPick best;
     auto consider = [&](int ti, int s, int sched) {
         const double us = model_us(ti, form, M, N, K, batch, s, taps, sched == 3, c_esz);
@@ -144,7 +145,7 @@ int stream_variant(const cb_gemm_desc* d, const Prepared& pr) {
     const GP& p = pr.p;
     if (!pr.fast || !pr.cv8 || d->dtype != CB_BF16 || pr.form != FORM_FWD || p.batch > 1 || p.split_k > 1) return -1;
     if (d->c_f32 || d->accumulate || d->c_rowmap || d->zero_fill_pitch || d->a_rowsum || d->gelu_grad_pre || d->dropout_p > 0.f || d->mask || d->relu_bwd ||
-        d->C2) return -1;
+        d->C2 || d->res_rowmap) return -1;
     if (d->K % 8 != 0 || d->M < 64) return -1;
     if ((int64_t)d->M * (d->N > d->K ? d->N : d->K) * 2 >= 0x7fffffffll) return -1;       // (32-bit byte offsets of the DMA loaders)
     if (p.ktiles == 1 && d->N % 256 == 0) return 0;
@@ -190,7 +191,11 @@ int gemm_choose(const cb_gemm_desc* d, const Prepared& pr, bool use_table, bool 
     const int sv = stream_variant(d, pr);
     CB_REQUIRE(d->tile != 8 || sv >= 0, "cb_gemm: tile 8 (streaming) does not cover this problem (M=%d N=%d K=%d modes %d/%d)", d->M, d->N, d->K, d->a_mode, d->b_mode);
     const cbgemm::TunedEntry* tabled =
-        (bf && use_table && !sw.no_tuned) ? cbgemm::tuned_lookup(d->a_mode, d->b_mode, d->M, d->N, d->K, p.batch, pr.taps, split_caller) : nullptr;
+        (bf && use_table && !sw.no_tuned && !d->dgrad_s2) ? cbgemm::tuned_lookup(d->a_mode, d->b_mode, d->M, d->N, d->K, p.batch, pr.taps, split_caller) : nullptr;
+    // A plain product the table does not know may be one it knows as a 1x1 strided gather: the first block of a stage behind a tail-form
+    // block (modeling/cnn.py) runs its stride-2 1x1 convolutions on the compact even-pixel tensor -- the same M x N x K, rows contiguous
+    if (!tabled && bf && use_table && !sw.no_tuned && pr.form == FORM_FWD)
+        tabled = cbgemm::tuned_lookup(CB_ROWK_GATHER, d->b_mode, d->M, d->N, d->K, p.batch, 1, split_caller);
     if (d->tile == 8 || (!explicit_tile && use_table && !sw.no_stream && !tabled && sv >= 0 && d->M >= STREAM_MIN_ROWS && d->N <= 512)) {
         lp.tile = 8; lp.sched = sv; lp.c_vec8 = true;
         return 0;
@@ -199,7 +204,8 @@ int gemm_choose(const cb_gemm_desc* d, const Prepared& pr, bool use_table, bool 
     // ---- one workgroup per tile.  8-wave LDS-DMA tiles: bf16 fast path, row-contiguous epilogue.  Their K split writes fp32 partial slabs
     // into the caller's scratch and a second kernel adds them in index order and applies the FULL epilogue: deterministic, no atomics,
     // any epilogue.  The 4-wave kernels split K only where the parts may combine through atomics.
-    const int form8 = (bf && pr.fast && pr.cv8 && (pr.form != FORM_DGRAD_TAPS || p.Ct % 64 == 0)) ? FORM8_OF[pr.form] : 0;
+    // (a residual row map and the stride-2 data gradient by classes exist in the 4-wave kernels only)
+    const int form8 = (bf && pr.fast && pr.cv8 && (pr.form != FORM_DGRAD_TAPS || p.Ct % 64 == 0) && !d->res_rowmap && !d->dgrad_s2) ? FORM8_OF[pr.form] : 0;
     const int64_t ws_room = assume_ws ? splitk_payload_bytes(WS_UNLIMITED)
                                       : (d->splitk_ws && aligned16(d->splitk_ws) ? splitk_payload_bytes(d->splitk_ws_bytes) : 0);
     // the 4-wave kernels may choose their own K split for a weight-gradient form accumulated in place.  (explicit_tile: a caller who names

@@ -23,14 +23,19 @@ template <> __device__ __forceinline__ int lds_off<float>(int row, int seg) { re
 struct GP {
     const void* A; const void* B; void* C; void* C2; const void* residual; const void* mask;
     const void* dact_pre; float* a_rowsum; int64_t ldd;
-    int relu_bwd; const float* post_scale; const float* post_scale2;   // ResNet-block ReLU x FrozenBN backward epilogue
-    int batch; int64_t bs_a, bs_b, bs_c, bs_r;      // strided-batched problems on gridDim.z (strides in BYTES; bs_r in floats)
+    int relu_bwd;
+    int cls_rows;               // cb_gemm_desc.dgrad_s2: rows per parity class (M / 4), 0: an ordinary problem (see dgrad_s2_class)
+    const float* post_scale; const float* post_scale2;   // ResNet-block ReLU x FrozenBN backward epilogue
+    int batch;
+    int fast_epi;               // index into FAST_EPI_COMBOS: the specialised epilogue of this call (fast_epilogue), 0: the generic epilogue8
+    int64_t bs_a, bs_b, bs_c, bs_r;      // strided-batched problems on gridDim.z (strides in BYTES; bs_r in floats)
     const float* scale; const float* shift;
     const cb_pixel* a_tab; const cb_pixel* b_tab; const int32_t* c_rowmap;
     int64_t lda, ldb, ldc, ldc2, ldr, ldm, sH, sW;
     int M, N, K;
     int a_mode, b_mode;
-    int R, S, Ct, H, W, flip;
+    int R, S, Ct, H, W;
+    int flip;                   // CB_KROW_TAPS: 0 tap t reads weight tap t, 1 the flipped one; >= TAP_S2: a parity class of dgrad_s2 (tap_weight)
     int c_f32, accumulate, split_k, act, relu_after;
     float alpha, dropout_p;
     uint64_t seed;
@@ -42,7 +47,7 @@ struct GP {
     uint32_t a_bytes, b_bytes;
     int ktiles;
     int slab_base, cnt_base;    // grouped launch with slab K split (gemm_tile): this problem's first slab unit / first tile counter
-    int fast_epi;               // index into FAST_EPI_COMBOS: the specialised epilogue of this call (fast_epilogue), 0: the generic epilogue8
+    const int32_t* res_rowmap;  // cb_gemm_desc.res_rowmap (4-wave kernels only)
     float* sq_slots;            // cb_gemm_desc.sq_slots (this problem's first slot): output tile t stores the sum of the squares of its C to sq_slots[t]
 #ifdef CB_STAMPS
     unsigned long long* stamps;   // diagnostic build only (tools/stamps_*.py): this launch's record area, or null
@@ -59,7 +64,9 @@ enum { EF_SCALE = 1, EF_SHIFT = 2, EF_RELU = 4, EF_GELU2 = 8, EF_DROP = 16, EF_R
        EF_RBWD = 512,      // cb_gemm_desc.relu_bwd: t = (acc [+ residual]) where mask > 0; C2 = t [* post_scale2]; C = t * post_scale
        EF_PS2 = 1024,
        EF_F32 = 2048,      // fp32 C STORED (accumulate 0 / 2), nothing else: the weight-gradient forms; + the tile's share of the squared norm
-       EF_GELU1 = 4096 };  // C = gelu(.), no second output (inference)
+       EF_GELU1 = 4096,    // C = gelu(.), no second output (inference)
+       EF_RMAP = 8192,     // the residual is read through GP::res_rowmap (-1: none for this row) -- 4-wave kernels only
+       EF_CMAP = 16384 };  // C and the mask live at row GP::c_rowmap[m] (the classes of cb_gemm_desc.dgrad_s2) -- 4-wave kernels only
 constexpr int FAST_EPI_COMBOS[] = {
     -1,                                                  // 0: generic
     0,                                                   // 1: C = acc                                  (data gradients without epilogue, grid conv)
@@ -79,6 +86,9 @@ constexpr int FAST_EPI_COMBOS[] = {
     EF_RBWD | EF_PS2 | EF_RES,
     EF_F32,                                              // 16: dW stored by its first writer (+ sum of squares to GP::sq_slots) -- weight-gradient kernels only
     EF_SHIFT | EF_GELU1,                                 // 17: C = gelu(. + bias)                        (BertIntermediate forward, inference)
+    EF_SCALE | EF_SHIFT | EF_RES | EF_RELU_AFTER | EF_RMAP,   // 18: 10 with the block input gathered at the even pixels (conv3 of a tail block)
+    EF_RBWD | EF_RES | EF_RMAP,                          // 19: 13 with the compact shortcut gradient scattered to the even pixels (conv1 dgrad of a tail block)
+    EF_SCALE | EF_MASK | EF_CMAP,                        // 20: 11 through the output row map (3x3 stride-2 data gradient by parity classes)
 };
 constexpr int FAST_EPI_F32 = 16;
 constexpr int FAST_EPI_N = sizeof(FAST_EPI_COMBOS) / sizeof(int);
@@ -140,6 +150,18 @@ __device__ __forceinline__ rsrc_t make_rsrc(const void* p, uint32_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
 }
 __device__ __forceinline__ u32x4 bload16(rsrc_t r, uint32_t off) { return __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0); }
+
+// CB_KROW_TAPS: the weight tap that reduction tap `tap` reads.  GP::flip >= TAP_S2 (set per workgroup by dgrad_s2_class): the taps of one
+// parity class of the 3x3 stride-2 data gradient -- window position (jr, js) of the R x S (1 or 2 each) window of g meets weight tap
+// (r0 - 2 jr, s0 - 2 js), and flip - TAP_S2 = 3 r0 + s0.
+constexpr int TAP_S2 = 16;
+__device__ __forceinline__ int tap_weight(const GP& p, int tap) {
+    if (p.flip >= TAP_S2) {
+        const int jr = p.S == 2 ? tap >> 1 : tap, js = p.S == 2 ? tap & 1 : 0;
+        return p.flip - TAP_S2 - 6 * jr - 2 * js;
+    }
+    return p.flip ? (p.R * p.S - 1 - tap) : tap;
+}
 
 // one operand of the GEMM as the loaders see it
 struct Opnd {
@@ -282,7 +304,7 @@ template <typename T, int ROWS, bool FAST> struct KrowLoader {
             const int nvalid = bound - row[it];
             int64_t ro = rowoff[it];
             if (mode == CB_KROW_TAPS) {
-                int tapw = p.flip ? (p.R * p.S - 1 - tap[it]) : tap[it];
+                int tapw = tap_weight(p, tap[it]);
                 ro = (int64_t)tapw * bound + row[it];
             }
 #pragma unroll
@@ -492,7 +514,7 @@ template <typename T, int ROWS, int KMODE, int KB_ = 4, int SHIFT = 0> struct Kr
                 voff[it] += X::BK * ldb;
                 kb0[it] += X::BK;
             } else if constexpr (KMODE == KM_TAPS) {        // (Ct % 8 == 0: a block never straddles a tap)
-                const int tapw = p.flip ? (p.R * p.S - 1 - tap[it]) : tap[it];
+                const int tapw = tap_weight(p, tap[it]);
                 const bool v = act[it] && tap[it] < p.R * p.S;
                 const uint32_t base = (uint32_t)co[it] * ldb + (uint32_t)tapw * bound * ESZ + voff[it];
 #pragma unroll
@@ -655,7 +677,7 @@ template <int ROWS, int KMODE> struct KrowTr {
                 voff[i] += X::BK * ldb;
                 kl[i] += X::BK;
             } else if constexpr (KMODE == KM_TAPS) {
-                const int tapw = p.flip ? (p.R * p.S - 1 - tap[i]) : tap[i];
+                const int tapw = tap_weight(p, tap[i]);
                 const bool v = act[i] && tap[i] < p.R * p.S;
                 st.r[i] = bload16(rs, v ? (uint32_t)co[i] * ldb + (uint32_t)tapw * bound * ESZ + voff[i] : OOB);
                 co[i] += X::BK;
@@ -715,6 +737,30 @@ __device__ __forceinline__ void apply_batch(GP& p, TileId& t) {
     if (p.a_rowsum) p.a_rowsum += b * p.bs_r;
 }
 
+// cb_gemm_desc.dgrad_s2: the four parity classes of a 3x3 stride-2 data gradient share one grid, each class tiled on its own (grid y =
+// 4 * ceil(cls_rows / BM), dgrad_s2_grid_y).  Along y the CLASS varies fastest, the four-tap class first: four consecutive workgroups
+// work on the same block of pixels -- the same rows of g, neighbouring output rows -- and every run of the grid holds the same mix of
+// 4-, 2-, 2- and 1-tap tiles.  (Class-major tiles, as the rows are laid out, put all four-tap tiles -- 4/9 of the work -- on the last two
+// of the eight XCDs under the XCD-compact order and at the end of the grid under the dispatch order: measured 45 / 35 us at
+// 50176 x 128 x 1152 against the figure in DESIGN.md for this order.)  A workgroup turns its copy of the parameter block into the ordinary
+// gather x CB_KROW_TAPS problem of ITS class (py, px): M = cls_rows rows, an R x S = (1 + py) x (1 + px) window of g at the table's pixel,
+// K = R * S * Ct, weight taps (1 + py - 2 jr, 1 + px - 2 js) (tap_weight), and the class's part of the output row map.  Everything after
+// this point -- loaders, K loop, epilogue -- is the code every data gradient runs.
+template <int BM, int BK>
+__device__ __forceinline__ void dgrad_s2_class(GP& p, TileId& bid) {
+    if (p.cls_rows <= 0) return;                                 // (block-uniform)
+    const int cls = 3 - (bid.by & 3);
+    bid.by >>= 2;
+    const int py = cls >> 1, px = cls & 1;
+    p.M = p.cls_rows;
+    p.R = 1 + py; p.S = 1 + px;
+    p.K = p.R * p.S * p.Ct;
+    p.ktiles = (p.K + BK - 1) / BK;
+    p.flip = TAP_S2 + 3 * (1 + py) + (1 + px);
+    p.c_rowmap += (int64_t)cls * p.cls_rows;
+}
+inline int dgrad_s2_grid_y(const GP& p, int BM) { return p.cls_rows > 0 ? 4 * ((p.cls_rows + BM - 1) / BM) : (p.M + BM - 1) / BM; }
+
 // ---------------------------------------------------------------------------------------------
 // Epilogue of one 4-wide accumulator fragment (row m, columns nb..nb+3).
 // ---------------------------------------------------------------------------------------------
@@ -742,13 +788,17 @@ __device__ __forceinline__ float scale_shift(float x, float sc, float sh) {
     }
 }
 
-template <typename T>
-__device__ __forceinline__ void epilogue_vec(const GP& p, f32x4 v, int m, int64_t orow, int nb) {
+// RMAP (here and in epilogue_elem / epilogue8): the residual is read at row `rrow` (GP::res_rowmap's entry, -1: none) instead of orow.
+// The 4-wave kernels' tile_epilogue instantiates RMAP = true only; every other caller keeps the code it had.
+template <typename T, bool RMAP = false>
+__device__ __forceinline__ void epilogue_vec(const GP& p, f32x4 v, int m, int64_t orow, int nb, int64_t rrow = 0) {
+    if constexpr (!RMAP) rrow = orow;
+    const bool has_res = p.residual != nullptr && (!RMAP || rrow >= 0);
     v = v * p.alpha;
     if (p.relu_bwd) {          // t = (acc [+ C] [+ residual]) where mask > 0;  C2 = t * post_scale2,  C = t * post_scale
         T* c = reinterpret_cast<T*>(p.C) + orow * p.ldc + nb;
         if (p.accumulate) v = v + load4(c);
-        if (p.residual) v = v + load4(reinterpret_cast<const T*>(p.residual) + orow * p.ldr + nb);
+        if (has_res) v = v + load4(reinterpret_cast<const T*>(p.residual) + rrow * p.ldr + nb);
         const f32x4 mk = load4(reinterpret_cast<const T*>(p.mask) + orow * p.ldm + nb);
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = mk[r] > 0.f ? v[r] : 0.f;
@@ -783,7 +833,7 @@ __device__ __forceinline__ void epilogue_vec(const GP& p, f32x4 v, int m, int64_
     if (p.dropout_p > 0.f) {
         v = v * dropout_mult4(p.seed, (uint64_t)m * ((p.N + 3) >> 2) + (nb >> 2), p.dropout_p);
     }
-    if (p.residual) v = v + load4(reinterpret_cast<const T*>(p.residual) + orow * p.ldr + nb);
+    if (has_res) v = v + load4(reinterpret_cast<const T*>(p.residual) + rrow * p.ldr + nb);
     if (p.relu_after) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
@@ -815,13 +865,15 @@ __device__ __forceinline__ void epilogue_vec(const GP& p, f32x4 v, int m, int64_
 }
 
 // one element (ragged / unaligned edge path; reached through the LDS-staged slow epilogue below)
-template <typename T>
-__device__ __forceinline__ void epilogue_elem(const GP& p, float x, int m, int64_t orow, int n) {
+template <typename T, bool RMAP = false>
+__device__ __forceinline__ void epilogue_elem(const GP& p, float x, int m, int64_t orow, int n, int64_t rrow = 0) {
+    if constexpr (!RMAP) rrow = orow;
+    const bool has_res = p.residual != nullptr && (!RMAP || rrow >= 0);
     x *= p.alpha;
     if (p.relu_bwd) {
         T* c = reinterpret_cast<T*>(p.C) + orow * p.ldc + n;
         if (p.accumulate) x += to_f32(*c);
-        if (p.residual) x += to_f32(reinterpret_cast<const T*>(p.residual)[orow * p.ldr + n]);
+        if (has_res) x += to_f32(reinterpret_cast<const T*>(p.residual)[rrow * p.ldr + n]);
         x = to_f32(reinterpret_cast<const T*>(p.mask)[orow * p.ldm + n]) > 0.f ? x : 0.f;
         if (p.C2) reinterpret_cast<T*>(p.C2)[orow * p.ldc2 + n] = from_f32<T>(p.post_scale2 ? x * p.post_scale2[n] : x);
         *c = from_f32<T>(p.post_scale ? x * p.post_scale[n] : x);
@@ -840,7 +892,7 @@ __device__ __forceinline__ void epilogue_elem(const GP& p, float x, int m, int64
         x = act_of<T>(p.act, x);
     }
     if (p.dropout_p > 0.f) x *= dropout_mult1(p.seed, (uint64_t)m * ((p.N + 3) >> 2) + (n >> 2), n & 3, p.dropout_p);
-    if (p.residual) x += to_f32(reinterpret_cast<const T*>(p.residual)[orow * p.ldr + n]);
+    if (has_res) x += to_f32(reinterpret_cast<const T*>(p.residual)[rrow * p.ldr + n]);
     if (p.relu_after) x = x > 0.f ? x : 0.f;
     if (p.mask) x = to_f32(reinterpret_cast<const T*>(p.mask)[orow * p.ldm + n]) > 0.f ? x : 0.f;
     if (p.dact_pre) {
@@ -910,14 +962,16 @@ __device__ __forceinline__ void zero_patch8(T* base, int64_t ld, int64_t orow, i
 #else
 #define CB_EPI_ST(...) do { __VA_ARGS__; } while (0)
 #endif
-template <typename T, int EPF = 0>
+template <typename T, int EPF = 0, bool RMAP = false>
 __device__ __forceinline__ void epilogue8(const GP& p, float (&v)[8], const float (&sc)[8], const float (&sh)[8],
-                                          int m, int64_t orow, int n, bf16x8 rpre = bf16x8{}, bf16x8 apre = bf16x8{}) {
+                                          int m, int64_t orow, int n, bf16x8 rpre = bf16x8{}, bf16x8 apre = bf16x8{}, int64_t rrow = 0) {
+    if constexpr (!RMAP) rrow = orow;
+    const bool has_res = p.residual != nullptr && (!RMAP || rrow >= 0);      // (a prefetched chunk of a row without residual holds zeros)
     auto load_res = [&](float (&t)[8]) {
         if constexpr (EPF == 2) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) t[r] = (float)rpre[r];
-        } else load8(reinterpret_cast<const T*>(p.residual) + orow * p.ldr + n, t);
+        } else load8(reinterpret_cast<const T*>(p.residual) + rrow * p.ldr + n, t);
     };
     auto load_aux = [&](const void* base, int64_t ld, float (&t)[8]) {
         if constexpr (EPF >= 1) {
@@ -944,7 +998,7 @@ __device__ __forceinline__ void epilogue8(const GP& p, float (&v)[8], const floa
 #pragma unroll
             for (int r = 0; r < 8; ++r) v[r] += t[r];
         }
-        if (p.residual) {
+        if (has_res) {
             load_res(t);
 #pragma unroll
             for (int r = 0; r < 8; ++r) v[r] += t[r];
@@ -1028,7 +1082,7 @@ __device__ __forceinline__ void epilogue8(const GP& p, float (&v)[8], const floa
 #pragma unroll
         for (int r = 0; r < 4; ++r) { v[r] *= d0[r]; v[4 + r] *= d1[r]; }
     }
-    if (p.residual) {
+    if (has_res) {
         float t[8];
         load_res(t);
 #pragma unroll
@@ -1123,10 +1177,14 @@ __device__ __forceinline__ void fast_epilogue(const GP& p, unsigned char* smem, 
     const uint32_t ldcb = (uint32_t)p.ldc * CESZ, ldc2b = (uint32_t)p.ldc2 * 2u, nb = (uint32_t)n * 2u;
     float sq = 0.f;                                              // EF_F32: this thread's share of sum(C^2)
     // operands are read through range-checked descriptors: rows past M (and chunks past N) take the out-of-range offset and read zeros
-    const rsrc_t rr = make_rsrc(HAS_RES ? p.residual : p.C, HAS_RES ? (uint32_t)((int64_t)p.M * p.ldr * 2) : 0u);
+    // (EF_RMAP: the residual has its own row count -- the host checked that it ends below 2 GiB, and a row without residual takes OOB)
+    constexpr bool RMAP = (FLAGS & EF_RMAP) != 0, CMAP = (FLAGS & EF_CMAP) != 0;
+    const rsrc_t rr = make_rsrc(HAS_RES ? p.residual : p.C, HAS_RES ? (RMAP ? OOB : (uint32_t)((int64_t)p.M * p.ldr * 2)) : 0u);
     const void* auxp = (FLAGS & (EF_MASK | EF_RBWD)) ? p.mask : p.dact_pre;
     const int64_t lda = (FLAGS & (EF_MASK | EF_RBWD)) ? p.ldm : p.ldd;
-    const rsrc_t ra = make_rsrc(HAS_AUX ? auxp : p.C, HAS_AUX ? (uint32_t)((int64_t)p.M * lda * 2) : 0u);
+    const rsrc_t ra = make_rsrc(HAS_AUX ? auxp : p.C, HAS_AUX ? (CMAP ? OOB : (uint32_t)((int64_t)p.M * lda * 2)) : 0u);
+    // (EF_CMAP: the mapped rows run over the whole output, which the host checked to end below 2 GiB)
+    auto out_row = [&](int m) __attribute__((always_inline)) { if constexpr (CMAP) return (uint32_t)p.c_rowmap[m]; else return (uint32_t)m; };
     const uint32_t ldrb = (uint32_t)p.ldr * 2u, ldab = (uint32_t)lda * 2u;
     f32x2 sc[4], sh[4];
 #pragma unroll
@@ -1158,11 +1216,14 @@ __device__ __forceinline__ void fast_epilogue(const GP& p, unsigned char* smem, 
             const int slot = (ALL ? h * ITER : 0) + it;
             if constexpr (HAS_RES) {
                 if (ALL && pre_r) { union { bf16x8 x; u32x4 r; } u; u.x = pre_r[h * ITER + it]; res[slot] = u.r; }
-                else res[slot] = bload16(rr, ok ? (uint32_t)m * ldrb + nb : OOB);
+                else if constexpr (RMAP) {
+                    const int rm = ok ? p.res_rowmap[m] : -1;
+                    res[slot] = bload16(rr, rm >= 0 ? (uint32_t)rm * ldrb + nb : OOB);
+                } else res[slot] = bload16(rr, ok ? (uint32_t)m * ldrb + nb : OOB);
             }
             if constexpr (HAS_AUX) {
                 if (ALL && pre_a) { union { bf16x8 x; u32x4 r; } u; u.x = pre_a[h * ITER + it]; aux[slot] = u.r; }
-                else aux[slot] = bload16(ra, ok ? (uint32_t)m * ldab + nb : OOB);
+                else aux[slot] = bload16(ra, ok ? out_row(ok ? m : 0) * ldab + nb : OOB);
             }
         }
     };
@@ -1247,7 +1308,7 @@ __device__ __forceinline__ void fast_epilogue(const GP& p, unsigned char* smem, 
                 else v[r] = v[r] * t[r];
             }
         }
-        __builtin_amdgcn_raw_buffer_store_b128(pack_bf16x8(v), rc, (uint32_t)m * ldcb + nb, 0, 16 /* sc1 */);
+        __builtin_amdgcn_raw_buffer_store_b128(pack_bf16x8(v), rc, out_row(m) * ldcb + nb, 0, 16 /* sc1 */);
     };
     auto pass = [&](int h) __attribute__((always_inline)) {
         if constexpr ((HAS_RES || HAS_AUX) && !ALL) request(h);
@@ -1300,10 +1361,12 @@ __device__ __forceinline__ void fast_epilogue(const GP& p, unsigned char* smem, 
 // 7.718 -> 7.701 ms per step, three alternating pairs (profiles/r06w_epilogue_bodies_per_form.txt) -- and see gemm8_impl.h
 // tile_epilogue8w for what ALL of them did to the 256x256 instantiation.
 __host__ __device__ constexpr bool fe_in_form(int idx, int form) {
-    if (form == 1) return idx == 1 || idx == 2 || idx == 3 || idx == 4 || idx == 5 || idx == 8 || idx == 9 || idx == 10 || idx == 17;
-    if (form == 2) return idx == 1 || idx == 6 || idx == 7 || (idx >= 11 && idx <= 15);
+    if (form == 1) return idx == 1 || idx == 2 || idx == 3 || idx == 4 || idx == 5 || idx == 8 || idx == 9 || idx == 10 || idx == 17 || idx == 18;
+    if (form == 2) return idx == 1 || idx == 6 || idx == 7 || (idx >= 11 && idx <= 15) || idx == 19 || idx == 20;
     return true;
 }
+// the row-map bodies (EF_RMAP, EF_CMAP) exist in the 4-wave kernels only (NT == NTHREADS): the 8-wave kernels never meet them (gemm_choose)
+__host__ __device__ constexpr bool fe_for_threads(int idx, int nt) { return (FAST_EPI_COMBOS[idx] & (EF_RMAP | EF_CMAP)) == 0 || nt == NTHREADS; }
 template <int NT, int BN, int PR, int NPASS, bool WG = false, int FORM = 0, typename StageFn>
 __device__ __forceinline__ void fast_epilogue_dispatch(const GP& p, unsigned char* smem, int m0, int n0, int tid, StageFn stage,
                                                        const bf16x8* pre_r = nullptr, const bf16x8* pre_a = nullptr, int tile_lin = 0) {
@@ -1312,14 +1375,14 @@ __device__ __forceinline__ void fast_epilogue_dispatch(const GP& p, unsigned cha
         return;
     }
     switch (p.fast_epi) {
-#define CB_FE_CASE(I) case I: if constexpr (fe_in_form(I, FORM)) fast_epilogue<FAST_EPI_COMBOS[I], NT, BN, PR, NPASS>(p, smem, m0, n0, tid, stage, pre_r, pre_a); break;
+#define CB_FE_CASE(I) case I: if constexpr (fe_in_form(I, FORM) && fe_for_threads(I, NT)) fast_epilogue<FAST_EPI_COMBOS[I], NT, BN, PR, NPASS>(p, smem, m0, n0, tid, stage, pre_r, pre_a); break;
         CB_FE_CASE(1) CB_FE_CASE(2) CB_FE_CASE(3) CB_FE_CASE(4) CB_FE_CASE(5) CB_FE_CASE(6) CB_FE_CASE(7) CB_FE_CASE(8) CB_FE_CASE(9) CB_FE_CASE(10)
-        CB_FE_CASE(11) CB_FE_CASE(12) CB_FE_CASE(13) CB_FE_CASE(14) CB_FE_CASE(15) CB_FE_CASE(17)
+        CB_FE_CASE(11) CB_FE_CASE(12) CB_FE_CASE(13) CB_FE_CASE(14) CB_FE_CASE(15) CB_FE_CASE(17) CB_FE_CASE(18) CB_FE_CASE(19) CB_FE_CASE(20)
 #undef CB_FE_CASE
         default: break;
     }
 }
-static_assert(FAST_EPI_N == 18 && FAST_EPI_COMBOS[FAST_EPI_F32] == EF_F32, "fast_epilogue_dispatch lists every combination");
+static_assert(FAST_EPI_N == 21 && FAST_EPI_COMBOS[FAST_EPI_F32] == EF_F32, "fast_epilogue_dispatch lists every combination");
 
 // ---------------------------------------------------------------------------------------------
 // Epilogue-operand prefetch (row-contiguous bf16 epilogue only).  The epilogue's global READS -- the residual and the ReLU mask
@@ -1353,7 +1416,8 @@ __device__ __forceinline__ void epi_prefetch(const GP& p, EpiPre<BM, BN, WITH_R>
             if (m < p.M && n < p.N) {
                 const int64_t orow = p.c_rowmap ? (int64_t)p.c_rowmap[m] : (int64_t)m;
                 if constexpr (WITH_R) {
-                    if (p.residual) pre.r[h * E::ITER + it] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const T*>(p.residual) + orow * p.ldr + n);
+                    const int64_t rrow = p.res_rowmap ? (int64_t)p.res_rowmap[m] : orow;          // (-1: the chunk stays zero)
+                    if (p.residual && rrow >= 0) pre.r[h * E::ITER + it] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const T*>(p.residual) + rrow * p.ldr + n);
                 }
                 if (aux) pre.a[h * E::ITER + it] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const T*>(aux) + orow * lda + n);
             }
@@ -1439,15 +1503,16 @@ __device__ __forceinline__ void tile_epilogue(GP& p, f32x4 (&acc)[BM / 32][BN / 
                 }
                 if (m < p.M && nok) {
                     const int64_t orow = p.c_rowmap ? (int64_t)p.c_rowmap[m] : (int64_t)m;
+                    const int64_t rrow = p.res_rowmap ? (int64_t)p.res_rowmap[m] : orow;
                     float v[8];
                     load8(reinterpret_cast<const float*>(smem + rl * SROW + cc * 32), v);
                     if constexpr (EPF == 2) {
-                        if (use_pre) epilogue8<T, 2>(p, v, sc, sh, m, orow, n, rp, ap);
-                        else epilogue8<T>(p, v, sc, sh, m, orow, n);
+                        if (use_pre) epilogue8<T, 2, true>(p, v, sc, sh, m, orow, n, rp, ap, rrow);
+                        else epilogue8<T, 0, true>(p, v, sc, sh, m, orow, n, bf16x8{}, bf16x8{}, rrow);
                     } else if constexpr (EPF == 1) {
-                        if (use_pre) epilogue8<T, 1>(p, v, sc, sh, m, orow, n, bf16x8{}, ap);
-                        else epilogue8<T>(p, v, sc, sh, m, orow, n);
-                    } else epilogue8<T>(p, v, sc, sh, m, orow, n);
+                        if (use_pre) epilogue8<T, 1, true>(p, v, sc, sh, m, orow, n, bf16x8{}, ap, rrow);
+                        else epilogue8<T, 0, true>(p, v, sc, sh, m, orow, n, bf16x8{}, bf16x8{}, rrow);
+                    } else epilogue8<T, 0, true>(p, v, sc, sh, m, orow, n, bf16x8{}, bf16x8{}, rrow);
                 }
             }
         }
@@ -1490,10 +1555,11 @@ __device__ __forceinline__ void tile_epilogue(GP& p, f32x4 (&acc)[BM / 32][BN / 
             const int m = m0 + wm * WM + i * 16 + (lane & 15);
             const bool mok = m < p.M;
             const int64_t orow = (mok && p.c_rowmap) ? (int64_t)p.c_rowmap[m] : (int64_t)m;
+            const int64_t rrow = (mok && p.res_rowmap) ? (int64_t)p.res_rowmap[m] : orow;
 #pragma unroll
             for (int j = 0; j < FN; ++j) {
                 const int nb = n0 + wn * WN + j * 16 + 4 * (lane >> 4);
-                if (mok) epilogue_vec<T>(p, acc[i][j], m, orow, nb);
+                if (mok) epilogue_vec<T, true>(p, acc[i][j], m, orow, nb, rrow);
             }
         }
     } else {
@@ -1517,7 +1583,7 @@ __device__ __forceinline__ void tile_epilogue(GP& p, f32x4 (&acc)[BM / 32][BN / 
                 const int m = m0 + h * WM + rl, n = n0 + cl;
                 if (m < p.M && n < p.N) {
                     const int64_t orow = p.c_rowmap ? (int64_t)p.c_rowmap[m] : (int64_t)m;
-                    epilogue_elem<T>(p, stage[idx], m, orow, n);
+                    epilogue_elem<T, true>(p, stage[idx], m, orow, n, p.res_rowmap ? (int64_t)p.res_rowmap[m] : orow);
                 }
             }
         }
@@ -1547,6 +1613,7 @@ __device__ __forceinline__ void gemm_tile(GP& p, TileId bid, float* slab = nullp
     // index of this output tile among the problem's tiles (batch member outermost; K parts of one tile share it): GP::sq_slots
     const int tile_lin = ((p.batch > 1 ? bid.bz / p.split_k : 0) * ((p.M + BM - 1) / BM) + bid.by) * ((p.N + BN - 1) / BN) + bid.bx;
     apply_batch(p, bid);
+    if constexpr (!LA::KROW && LB::KROW) dgrad_s2_class<BM, BK>(p, bid);
     const int m0 = bid.by * BM, n0 = bid.bx * BN;
     const int kt_per = (p.ktiles + p.split_k - 1) / p.split_k;
     const int kt0 = bid.bz * kt_per;
@@ -1913,7 +1980,7 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 template <typename T, int BM, int BN, int PF, int OCC, typename LA, typename LB, bool RS = false>
 int launch_k(const GP& p, hipStream_t st) {
-    dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, p.split_k * (p.batch > 1 ? p.batch : 1));
+    dim3 grid((p.N + BN - 1) / BN, dgrad_s2_grid_y(p, BM), p.split_k * (p.batch > 1 ? p.batch : 1));
     hipLaunchKernelGGL((gemm_kernel<T, BM, BN, LA, LB, PF, RS, OCC>), grid, dim3(NTHREADS), 0, st, p);
     return cb_launch_status("cb_gemm");
 }

@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(256) gemm_skinny_kernel(GP p, int a_vec, int b
 // does tile 9 cover this (prepared) problem?  bf16, plain k-contiguous A, B k-contiguous or reduction-major (aligned lines), one problem, no K split
 bool skinny_covers(const cb_gemm_desc* d, const GP& p) {
     if (d->dtype != CB_BF16 || d->a_mode != CB_ROWK || (d->b_mode != CB_ROWK && d->b_mode != CB_KROW)) return false;
-    if (p.batch > 1 || p.split_k > 1 || d->zero_fill_pitch || d->a_rowsum || d->sq_slots || d->accumulate == 2) return false;
+    if (p.batch > 1 || p.split_k > 1 || d->zero_fill_pitch || d->a_rowsum || d->sq_slots || d->accumulate == 2 || d->res_rowmap) return false;
     if (d->b_mode == CB_KROW && !(d->N % 8 == 0 && d->ldb % 8 == 0 && aligned16(d->B))) return false;
     return true;
 }

@@ -46,6 +46,11 @@ def _problem(d) -> dict:
     # algorithmic reduction length (SURVEY 8d counts algorithmic flops): the 7x7x3 stem is LAUNCHED on the zero-padded NHWC4 image
     # with K = 7 rows x (8 taps x 4 channels) = 224, of which 7 x 7 x 3 = 147 products per output are the convolution's
     K_alg = 147 if (d.a_mode == ops.ROWK_GATHER and int(d.R) == 7 and int(d.Cin) == 32 and K == 224) else K
+    # 3x3 stride-2 data gradient by parity classes (cb_gemm_desc.dgrad_s2): M / 4 rows each reduce over 1, 2, 2 and 4 of the 9 taps -- the
+    # sum over the classes is 2 (M / 4) N K; the gathered gradient has M / 4 rows
+    s2 = bool(d.dgrad_s2)
+    if s2:
+        K_alg = K / 4
     # pixel counts of a 224-multiple input are multiples of 49 (7 x 7 at res5); token rows (41 per pair) and head rows are not
     cnn = cnn or (wgrad and K % 49 == 0 and K >= 49) or (not wgrad and M % 49 == 0 and M >= 49 * 16)
     if wgrad:
@@ -60,9 +65,9 @@ def _problem(d) -> dict:
         else:
             fam = "encoder linear (fwd + dgrad)"
         extra = sum(1 for p in (d.residual, d.mask, d.C2, d.gelu_grad_pre) if p) + (1 if d.accumulate else 0) + (2 if d.relu_bwd else 0)
-        alg = batch * ((M * K / taps + N * K) * esz + M * N * c_esz + extra * M * N * esz)
+        alg = batch * (((M // 4 if s2 else M) * K / taps + N * K) * esz + M * N * c_esz + extra * M * N * esz)
     return {"family": fam, "flop": 2.0 * M * N * K_alg * batch, "bytes": float(alg), "M": M, "N": N, "K": K, "batch": batch, "taps": taps,
-            "form": "wgrad" if wgrad else ("dgrad" if d.b_mode in (ops.KROW, ops.KROW_TAPS) else "fwd")}
+            "form": "wgrad" if wgrad else ("dgrad" if d.b_mode in (ops.KROW, ops.KROW_TAPS) else "fwd"), "s2": s2}
 
 
 class GemmLog:

@@ -8,7 +8,7 @@ from .. import ops
 from ..data import RawFrames
 from ..ops import ACT_NONE, ACT_RELU, KROW, KROW_GATHER, KROW_TAPS, ROWK_GATHER
 from .modules import RESNET50_STAGES, BottleneckBlock, Conv2d, _Detectron2Model, _GridConv, as_config
-from .runtime import Runtime, _pick_split
+from .runtime import Runtime, _pick_split, even_pixel_index, even_pixel_rows, parity_class_rows
 
 
 def _out_hw(h, w, k, stride, pad):
@@ -29,7 +29,19 @@ def conv_gather(rt: Runtime, operand, n, h, w, c, k, stride, pad, device, out_hw
     return kw
 
 
-def _conv_fwd(rt: Runtime, x, conv, act=ACT_NONE, residual=None, relu_after=False):
+class _ConvAs:
+    """A convolution of the model run at another stride -- same weight, FrozenBN and window.  Stride 2 -> 1: the 1x1 stride-2 convolutions
+    of a stage's first block on an input that holds the even pixels only (they are plain products there).  Stride 1 -> 2: the 3x3
+    convolution of a tail block, whose output is read at the even pixels only."""
+    def __init__(self, conv, stride):
+        self.conv, self.stride = conv, stride
+
+    def __getattr__(self, name):
+        return getattr(self.conv, name)
+
+
+def _conv_fwd(rt: Runtime, x, conv, act=ACT_NONE, residual=None, relu_after=False, res_rowmap=None):
+    """``res_rowmap``: the residual is a tensor of other rows, read through this map (output row -> residual row)"""
     n, h, w, cin = x.shape
     k, s, p = conv.k, conv.stride, conv.pad
     oh, ow = _out_hw(h, w, k, s, p)
@@ -38,19 +50,21 @@ def _conv_fwd(rt: Runtime, x, conv, act=ACT_NONE, residual=None, relu_after=Fals
     y = torch.empty(n, oh, ow, cout, dtype=x.dtype, device=x.device)
     wk = rt.bank.compute(conv.weight).view(cout, k * k * cin)
     scale, shift = conv.scale_shift()
-    res2d = residual.view(m, cout) if residual is not None else None
+    res2d = residual.view(-1, cout) if residual is not None else None
     plain = k == 1 and s == 1                          # the image itself is the (m, cin) operand
     gather = {} if plain else conv_gather(rt, "a", n, h, w, cin, k, s, p, x.device)
     ops.gemm(x.view(m, cin) if plain else x, wk, m, cout, k * k * cin, out=y.view(m, cout), ldb=k * k * cin, **gather, scale=scale, shift=shift,
-             act=act, residual=res2d, relu_after=relu_after)
+             act=act, residual=res2d, relu_after=relu_after, res_rowmap=res_rowmap)
     return y
 
 
-def _conv_dgrad(rt: Runtime, g, conv, in_shape, scale=None, mask=None, residual=None, out=None, accumulate=False, fuse=None):
+def _conv_dgrad(rt: Runtime, g, conv, in_shape, scale=None, mask=None, residual=None, out=None, accumulate=False, fuse=None, res_rowmap=None):
     """d(input) of a convolution given g = d(conv output) (already multiplied by the FrozenBN scale).
     Epilogue options: per-channel ``scale`` and ReLU ``mask`` of the PRODUCER of the input, ``residual``.
     ``fuse = (y, s_a, s_b)``: the input is the output y of a ResNet block; the launch also does that block's ReLU x
-    FrozenBN-scale backward and returns (t*s_a, t*s_b) with t = d(input) where y > 0 (s_b None -> t itself)."""
+    FrozenBN-scale backward and returns (t*s_a, t*s_b) with t = d(input) where y > 0 (s_b None -> t itself).
+    ``res_rowmap``: the residual exists at some input pixels only (input row -> its row, or -1).
+    A 3x3 stride-2 convolution (the tail form's conv2) takes the one-launch parity-class form, cb_gemm_desc.dgrad_s2."""
     n, h, w, cin = in_shape
     _, oh, ow, cout = g.shape
     k, s, p = conv.k, conv.stride, conv.pad
@@ -59,11 +73,11 @@ def _conv_dgrad(rt: Runtime, g, conv, in_shape, scale=None, mask=None, residual=
     # stride-2 1x1 convolution: only the even pixels receive a gradient.  When the 2x2 patches tile the input exactly the launch
     # itself writes the zeros of the other three pixels (zero_fill_pitch); otherwise the output is pre-zeroed
     zfill = w if (k == 1 and s == 2 and h % 2 == 0 and w % 2 == 0 and cin % 8 == 0) else 0
-    alloc = torch.zeros if (s > 1 and not zfill) else torch.empty
+    alloc = torch.zeros if (k == 1 and s > 1 and not zfill) else torch.empty       # (the 3x3 stride-2 form writes every input pixel)
     if out is None:
         out = alloc(n, h, w, cin, dtype=g.dtype, device=g.device)
     o2 = out.view(mi, cin)
-    r2 = residual.view(mi, cin) if residual is not None else None
+    r2 = residual.view(-1, cin) if residual is not None else None
     k2 = mask.view(mi, cin) if mask is not None else None
     extra = {}
     second = None
@@ -77,7 +91,13 @@ def _conv_dgrad(rt: Runtime, g, conv, in_shape, scale=None, mask=None, residual=
         rowmap = rt.strided_rowmap(n, h, w, oh, ow, s, g.device) if s > 1 else None
         ops.gemm(g.view(n * oh * ow, cout), wk, n * oh * ow, cin, cout, out=o2, b_mode=KROW_TAPS, ldb=cin, R=1, S=1,
                  Cin=cout, c_rowmap=rowmap, scale=scale, mask=k2, residual=r2, accumulate=accumulate, zero_fill_pitch=zfill if s > 1 else 0,
-                 **extra)
+                 res_rowmap=res_rowmap, **extra)
+    elif s == 2:
+        assert k == 3 and p == 1 and h == 2 * oh and w == 2 * ow and residual is None and fuse is None and not accumulate
+        # the windows of the compact g that meet each parity class of input pixels are dense: its stride-1 pad-0 table serves all four
+        ops.gemm(g, wk, mi, cin, 9 * cout, out=o2, b_mode=KROW_TAPS, ldb=9 * cin, dgrad_s2=True,
+                 **conv_gather(rt, "a", n, oh, ow, cout, 3, 1, 0, g.device, out_hw=(oh, ow)), c_rowmap=rt.rowmap(parity_class_rows, n, h, w, g.device),
+                 scale=scale, mask=k2)
     else:
         assert s == 1
         # (the transposed convolution: the k x k windows of g under padding k - 1 - p, taps flipped)
@@ -153,6 +173,52 @@ def _res2_fusable(rt: Runtime, x, blk: BottleneckBlock, save: bool) -> bool:
             and c3.k == 1 and c1.cin in (64, 256) and (blk.shortcut is not None) == (c1.cin == 64) and x.shape[-1] == c1.cin and x.is_contiguous())
 
 
+def _reads_even_pixels_only(blk: BottleneckBlock) -> bool:
+    """a stage's first block under STRIDE_IN_1X1: its input is read by two 1x1 stride-2 convolutions, i.e. at the pixels (2i, 2j) only"""
+    sc, c1 = blk.shortcut, blk.conv1
+    return sc is not None and all(c.k == 1 and c.stride == 2 and c.pad == 0 for c in (sc, c1))
+
+
+def _tail_form(blk: BottleneckBlock, nxt: Optional[BottleneckBlock], x) -> bool:
+    """The TAIL FORM of a bottleneck block: it is the last of its stage, the only reader of its output is a block that samples the even
+    pixels, and the map is even-sized -- so three of every four output pixels are dead.  conv1 still runs on the whole map; conv2 runs as a
+    3x3 stride-2 convolution and conv3 + FrozenBN + shortcut + ReLU on the quarter map; the next block's stride-2 1x1 convolutions become
+    plain products on that compact tensor.  In the backward the dead pixels carried exact zeros: the same sums without them."""
+    c1, c2, c3 = blk.conv1, blk.conv2, blk.conv3
+    return (nxt is not None and _reads_even_pixels_only(nxt) and blk.shortcut is None and x.shape[1] % 2 == 0 and x.shape[2] % 2 == 0
+            and c1.k == 1 and c1.stride == 1 and c2.k == 3 and c2.stride == 1 and c2.pad == 1 and c3.k == 1 and c3.stride == 1
+            and c1.cin % 8 == 0 and c2.cin % 8 == 0 and c3.cin % 8 == 0)
+
+
+def blocks_forward(rt: Runtime, x, stages, save: bool, tail: bool = True):
+    """The bottleneck blocks of ``stages`` (a list of block lists) on x (n, h, w, c) -> (output, saved).  saved: one record
+    (blk, x, y1, y2, out, tail, compact_in) per trainable block when ``save``; tail: the block ran in its tail form (y2 and out hold the
+    even pixels only); compact_in: x is such an output, and the block's stride-2 1x1 convolutions ran as plain products on it."""
+    saved = []
+    flat = [(blk, stage[i + 1] if i + 1 < len(stage) else (stages[si + 1][0] if si + 1 < len(stages) and stages[si + 1] else None), i + 1 == len(stage))
+            for si, stage in enumerate(stages) for i, blk in enumerate(stage)]
+    compact_in = False
+    for blk, nxt, last in flat:
+        if not compact_in and _res2_fusable(rt, x, blk, save):
+            x = _res2_block_fused(rt, x, blk)
+            continue
+        as_tail = tail and last and _tail_form(blk, nxt, x)
+        c1, csc = (_ConvAs(blk.conv1, 1), _ConvAs(blk.shortcut, 1)) if compact_in else (blk.conv1, blk.shortcut)
+        sc = _conv_fwd(rt, x, csc) if blk.shortcut is not None else x
+        y1 = _conv_fwd(rt, x, c1, act=ACT_RELU)
+        if as_tail:
+            n, h, w, _ = x.shape
+            y2 = _conv_fwd(rt, y1, _ConvAs(blk.conv2, 2), act=ACT_RELU)
+            out = _conv_fwd(rt, y2, blk.conv3, residual=sc, relu_after=True, res_rowmap=rt.rowmap(even_pixel_rows, n, h, w, x.device))
+        else:
+            y2 = _conv_fwd(rt, y1, blk.conv2, act=ACT_RELU)
+            out = _conv_fwd(rt, y2, blk.conv3, residual=sc, relu_after=True)
+        if save and _block_trainable(rt, blk):
+            saved.append((blk, x, y1, y2, out, as_tail, compact_in))
+        x, compact_in = out, as_tail
+    return x, saved
+
+
 def _stem_forward(bb: "GridFeatBackbone", x5):
     """frames -> stem convolution + FrozenBN + ReLU + 3x3/2 max-pool (n, h/4, w/4, 64).  Raw frames / uint8 / float input, each
     through the fused launch (bf16, even width: the 112 x 112 x 64 map never leaves the CU) or as packed image -> GEMM -> pool."""
@@ -198,19 +264,7 @@ def cnn_forward(bb: "GridFeatBackbone", x5, save: bool):
     b, t = x5.shape[:2]
     net = bb.feature.backbone
     x = _stem_forward(bb, x5)
-    saved = []
-    for name, _nb, _mid, _cout, _s in RESNET50_STAGES:
-        for blk in getattr(net, name):
-            if _res2_fusable(rt, x, blk, save):
-                x = _res2_block_fused(rt, x, blk)
-                continue
-            sc = _conv_fwd(rt, x, blk.shortcut) if blk.shortcut is not None else x
-            y1 = _conv_fwd(rt, x, blk.conv1, act=ACT_RELU)
-            y2 = _conv_fwd(rt, y1, blk.conv2, act=ACT_RELU)
-            out = _conv_fwd(rt, y2, blk.conv3, residual=sc, relu_after=True)
-            if save and _block_trainable(rt, blk):
-                saved.append((blk, x, y1, y2, out))
-            x = out
+    x, saved = blocks_forward(rt, x, [list(getattr(net, name)) for name, *_ in RESNET50_STAGES], save)
     gconv = bb.grid_encoder[0]
     gy = _conv_fwd(rt, x, gconv)
     grid = ops.maxpool_fwd(gy, 2, 2, 0, relu=True)
@@ -247,39 +301,60 @@ def cnn_backward_steps(bb: "GridFeatBackbone", saved_pack, dgrid: torch.Tensor):
         ops.gemm_group(pend, dg)
         pend.clear()
 
-    def fuse_spec(i):
-        """the ReLU x FrozenBN-scale backward of block i, done by the launch that produces d(output of block i)"""
-        b, _x, _y1, _y2, o = saved[i]
-        s3_, _ = b.conv3.scale_shift()
-        ssc_ = b.shortcut.scale_shift()[0] if b.shortcut is not None else None
-        return (o, s3_, ssc_)
-
     # (g3, sec): g3 = d(conv3 output of the block), sec = d(identity shortcut) or d(shortcut conv output)
-    g3, sec = _conv_dgrad(rt, dg, gconv, res5.shape, fuse=fuse_spec(len(saved) - 1))
+    g3, sec = _conv_dgrad(rt, dg, gconv, res5.shape, fuse=_fuse_spec(saved[-1]))
+    yield from blocks_backward(rt, saved, g3, sec, stage_of, flush, pend, first_res5)
+
+
+def _fuse_spec(rec):
+    """the ReLU x FrozenBN-scale backward of a saved block, done by the launch that produces d(output of that block)"""
+    b, o = rec[0], rec[4]
+    s3_, _ = b.conv3.scale_shift()
+    ssc_ = b.shortcut.scale_shift()[0] if b.shortcut is not None else None
+    return (o, s3_, ssc_)
+
+
+def blocks_backward(rt: Runtime, saved, g3, sec, stage_of, flush, pend, first_res5=None, dx_out=None):
+    """Generator over the backward of the saved blocks (blocks_forward's records), last to first, from (g3, sec) of the last one; yields
+    where cnn_backward_steps documents.  ``dx_out`` (a list): d(input of the first saved block) is computed too and appended.
+    A tail-form block works on the quarter map from the launches that produce its (g3, sec) down to its conv2: the 3x3 stride-2 data
+    gradient (one launch, by parity classes) is where the chain returns to the whole map, and the block's conv1 data gradient adds the
+    compact identity-shortcut gradient at the even pixels through a row map."""
     for idx in range(len(saved) - 1, -1, -1):
-        blk, x, y1, y2, out = saved[idx]
-        need_dx = idx > 0
+        blk, x, y1, y2, out, tail, compact_in = saved[idx]
+        need_dx = idx > 0 or dx_out is not None
         s2, _ = blk.conv2.scale_shift()
         s1, _ = blk.conv1.scale_shift()
         dz, gsc = (sec, None) if blk.shortcut is None else (None, sec)
+        c1, csc = (_ConvAs(blk.conv1, 1), _ConvAs(blk.shortcut, 1)) if compact_in else (blk.conv1, blk.shortcut)
+        c2 = _ConvAs(blk.conv2, 2) if tail else blk.conv2
         _conv_wgrad(rt, g3, y2, blk.conv3, pend)
         if blk.shortcut is not None:
-            _conv_wgrad(rt, gsc, x, blk.shortcut, pend)
+            _conv_wgrad(rt, gsc, x, csc, pend)
         g2 = _conv_dgrad(rt, g3, blk.conv3, y2.shape, scale=s2, mask=y2)       # -> d(conv2 out) * mask * scale2
-        _conv_wgrad(rt, g2, y1, blk.conv2, pend)
-        g1 = _conv_dgrad(rt, g2, blk.conv2, y1.shape, scale=s1, mask=y1)
-        _conv_wgrad(rt, g1, x, blk.conv1, pend)
+        _conv_wgrad(rt, g2, y1, c2, pend)
+        g1 = _conv_dgrad(rt, g2, c2, y1.shape, scale=s1, mask=y1)
+        _conv_wgrad(rt, g1, x, c1, pend)
         if idx == 0 or stage_of.get(id(saved[idx - 1][0])) != stage_of.get(id(blk)):
             flush()                                     # the chain leaves this stage: its weight gradients in a few grouped launches
         if idx == first_res5 and idx > 0:
             yield "grid_encoder+res5"
         if need_dx:
-            spec = fuse_spec(idx - 1)
+            n, h, w, _ = x.shape
+            if idx > 0:
+                spec = _fuse_spec(saved[idx - 1])
             if blk.shortcut is None:
-                g3, sec = _conv_dgrad(rt, g1, blk.conv1, x.shape, residual=dz, fuse=spec)
+                rmap = dict(res_rowmap=rt.rowmap(even_pixel_index, n, h, w, x.device)) if tail else {}
+                if idx > 0:
+                    g3, sec = _conv_dgrad(rt, g1, c1, x.shape, residual=dz, fuse=spec, **rmap)
+                else:
+                    dx_out.append(_conv_dgrad(rt, g1, c1, x.shape, residual=dz, **rmap))
             else:
-                dout = _conv_dgrad(rt, g1, blk.conv1, x.shape)
-                g3, sec = _conv_dgrad(rt, gsc, blk.shortcut, x.shape, out=dout, accumulate=True, fuse=spec)
+                dout = _conv_dgrad(rt, g1, c1, x.shape)
+                if idx > 0:
+                    g3, sec = _conv_dgrad(rt, gsc, csc, x.shape, out=dout, accumulate=True, fuse=spec)
+                else:
+                    dx_out.append(_conv_dgrad(rt, gsc, csc, x.shape, out=dout, accumulate=True))
 
 
 class _CnnFn(torch.autograd.Function):

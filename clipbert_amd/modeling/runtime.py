@@ -9,6 +9,26 @@ from ..params import ParamBank
 _HOOK = {"encoder": "after_encoder_backward", "cnn": "after_res5_backward"}
 
 
+def even_pixel_rows(n, h, w):
+    """rows of the (n * h * w)-row image of an (n, h, w) map that hold its even pixels (2i, 2j), in (n, i, j) order"""
+    return (torch.arange(n).view(n, 1, 1) * (h * w) + (torch.arange(0, h, 2)).view(1, -1, 1) * w + torch.arange(0, w, 2).view(1, 1, -1)).reshape(-1)
+
+
+def parity_class_rows(n, h, w):
+    """output row map of the 3x3 stride-2 data gradient by parity classes (cb_gemm_desc.dgrad_s2) onto an (n, h, w) map, h and w even:
+    class-major, class = 2 * (y & 1) + (x & 1), each class in the (n, y >> 1, x >> 1) order of the compact gradient's pixel table"""
+    even = even_pixel_rows(n, h, w)
+    return torch.cat([even + py * w + px for py in (0, 1) for px in (0, 1)])
+
+
+def even_pixel_index(n, h, w):
+    """per row of the (n, h, w) map: the row of the compact even-pixel image that holds it, -1 for the other three pixels of each 2 x 2 patch"""
+    even = even_pixel_rows(n, h, w)
+    t = torch.full((n * h * w,), -1, dtype=torch.int64)
+    t[even] = torch.arange(even.numel())
+    return t
+
+
 class Runtime:
     def __init__(self):
         self.bank: Optional[ParamBank] = None
@@ -61,6 +81,14 @@ class Runtime:
             t = (torch.arange(n).view(n, 1, 1) * (h * w) + (torch.arange(oh) * stride).view(1, oh, 1) * w
                  + (torch.arange(ow) * stride).view(1, 1, ow)).reshape(-1).to(torch.int32).to(device)
             self.rowmaps[key] = t
+        return t
+
+    def rowmap(self, kind, n, h, w, device):
+        """cached int32 device copy of even_pixel_rows / parity_class_rows / even_pixel_index (``kind``: the function)"""
+        key = (kind.__name__, n, h, w, str(device))
+        t = self.rowmaps.get(key)
+        if t is None:
+            t = self.rowmaps[key] = kind(n, h, w).to(torch.int32).to(device)
         return t
 
 

@@ -53,7 +53,8 @@ def gemm_desc(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, *, out: 
               sH=0, sW=0, flip_taps=False, c_rowmap=None, accumulate=False, split_k=1, act=ACT_NONE,
               scale=None, shift=None, residual=None, ldr=None, relu_after=False, mask=None, ldm=None,
               out2=None, ldc2=None, alpha=1.0, dropout_p=0.0, dropout_seed=0, seed_ptr=None, tile=0, gelu_grad_pre=None, a_rowsum=None, batch=1, batch_strides=None,
-              relu_bwd=False, post_scale=None, post_scale2=None, xcd_order=0, zero_fill_pitch=0, splitk_ws=None, schedule=0, sq_slots=None) -> GemmDesc:
+              relu_bwd=False, post_scale=None, post_scale2=None, xcd_order=0, zero_fill_pitch=0, splitk_ws=None, schedule=0, sq_slots=None,
+              res_rowmap=None, dgrad_s2=False) -> GemmDesc:
     """The cb_gemm_desc of C[M,N] (op)= epilogue(sum_k A(m,k) B(n,k)); see include/clipbert_hip.h.  ``splitk_ws``: fp32 scratch for
     the K split of the 8-wave tiles (default: the per-device workspace of ``splitk_workspace``).  The descriptor borrows the
     tensors' memory: the caller keeps them alive until the launch that consumes it has been enqueued (``_refs`` holds them)."""
@@ -79,6 +80,10 @@ def gemm_desc(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, *, out: 
     d.scale, d.shift = _ptr(scale), _ptr(shift)
     d.residual = _ptr(residual)
     d.ldr = (ldr if ldr is not None else residual.stride(0)) if residual is not None else 0
+    if res_rowmap is not None:                # the residual through its own int32 row map (entry -1: none for that row)
+        assert residual is not None and res_rowmap.dtype == torch.int32 and res_rowmap.numel() == M
+        d.res_rowmap, d.res_rows = _ptr(res_rowmap), residual.shape[0]
+    d.dgrad_s2 = int(dgrad_s2)                # 3x3 stride-2 data gradient by parity classes (cb_gemm_desc.dgrad_s2)
     d.relu_after = int(relu_after)
     d.mask = _ptr(mask)
     d.ldm = (ldm if ldm is not None else mask.stride(0)) if mask is not None else 0
@@ -119,7 +124,7 @@ def gemm_desc(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, *, out: 
         assert sq_slots.dtype == torch.float32 and sq_slots.is_contiguous()
         d.sq_slots, d.sq_slots_n = _ptr(sq_slots), sq_slots.numel()
     d._refs = (a, b, out, a_tab, b_tab, c_rowmap, scale, shift, residual, mask, out2, seed_ptr, gelu_grad_pre, a_rowsum, post_scale,
-               post_scale2, splitk_ws, sq_slots)
+               post_scale2, splitk_ws, sq_slots, res_rowmap)
     return d
 
 

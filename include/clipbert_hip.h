@@ -142,6 +142,26 @@ typedef struct {
                                  (cb_sq_sum_fold): a deterministic norm without a second pass over the gradients.  A call that cannot
                                  honour it (another epilogue, unaligned rows, fp32 operands) FAILS rather than skip it silently. */
     int64_t sq_slots_n;
+    const int32_t* res_rowmap; /* optional row map of `residual` alone: the residual of GEMM row m is read at row res_rowmap[m] of the residual
+                                 tensor (M entries, indexed by the GEMM row, not the c_rowmap row); -1: no residual for this row.  Lets a
+                                 product over a SUBSET of the pixels of a map add the map's rows (conv3 of a bottleneck block computed at
+                                 the even pixels only, plus the block input there) and a product over the whole map add a tensor that
+                                 exists at a subset (the compact identity-shortcut gradient inside a full-map data gradient).
+                                 4-wave tiles only (tile 0 - 4); one problem per launch (no batch, not grouped). */
+    int32_t res_rows;         /* with res_rowmap: rows of the residual tensor (every map entry is -1 or < res_rows) */
+    int32_t dgrad_s2;         /* 1: data gradient of a 3x3 STRIDE-2 pad-1 convolution in ONE launch, by parity classes.  Input pixel (y, x)
+                                 receives g(oy, ox) * w(r, s) only for r = y + 1 - 2 oy, s = x + 1 - 2 ox: the class (y & 1, x & 1) decides
+                                 which of the nine taps exist -- (0,0): the centre tap; (0,1) / (1,0): two; (1,1): the four corners -- and the
+                                 rows of g that meet them form a dense (1 + (y & 1)) x (1 + (x & 1)) window at (y >> 1, x >> 1).  So:
+                                   A = g, the (n, H/2, W/2, Cin) gradient of the convolution's output, CB_ROWK_GATHER; a_tab = the stride-1
+                                       pad-0 pixel table of that map (M / 4 entries, shared by the four classes); H, W, sH, sW describe g;
+                                   B = the KRSC weights, CB_KROW_TAPS, ldb = 9 * N, R = S = 3, K = 9 * Cin (the algorithmic reduction: the
+                                       classes run 1, 2, 2 and 4 taps of it, 9 in all);
+                                   M = 4 * (M / 4) rows in CLASS-MAJOR order, class = 2 * (y & 1) + (x & 1), each class in the order of a_tab;
+                                   c_rowmap (required, M entries) sends row m to its input pixel; mask / scale / the other epilogue
+                                       operands are read at that mapped row, as with any c_rowmap.
+                                 Window rows past the edge of g (class (1, .) at y = H - 1) read zeros.  Output tiles never straddle a class
+                                 (each class is tiled on its own).  4-wave tiles only; one problem per launch; flip_taps is ignored. */
 } cb_gemm_desc;
 
 /* GEMM / implicit-GEMM convolution, all forms.  Replaces torch.nn.Linear / F.conv2d (+ apex-amp
@@ -546,7 +566,9 @@ const char* cb_last_error(void);
  * 10 = cb_resize_pack_yuv420 (the raw-frame ingest from I420 / NV12 planes; nothing else changed);
  * 11 = cb_mlm_select, cb_mlm_loss_fwd, cb_mlm_loss_bwd (the masked-LM head over the labelled rows only; nothing else changed);
  * 12 = cb_copy_ranges (batch staging for captured task loops; nothing else changed);
- * 13 = cb_vqa_loss_fwd, cb_vqa_loss_bwd (the image-VQA head over sparse answers; nothing else changed) */
+ * 13 = cb_vqa_loss_fwd, cb_vqa_loss_bwd (the image-VQA head over sparse answers; nothing else changed);
+ * 14 = cb_gemm_desc grew by res_rowmap / res_rows / dgrad_s2 at its END (zero = off: the residual through a row map of its own and the
+ *      3x3 stride-2 data gradient by parity classes -- the "tail form" of a bottleneck block whose consumer reads even pixels only) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------

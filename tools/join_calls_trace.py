@@ -13,7 +13,7 @@ import json
 import sys
 
 GEMM = ("gemm_kernel", "gemm8_kernel", "gemm_dma_kernel", "gemm_group_kernel", "gemm8p_kernel", "gemm_stream_kernel", "gemm_streamk_kernel",
-        "res2_block_kernel", "stem_pool_kernel")
+        "res2_block_kernel", "stem_pool_kernel", "skinny_kernel")
 
 
 def main():
@@ -21,8 +21,15 @@ def main():
     f = gzip.open(sys.argv[2]) if sys.argv[2].endswith(".gz") else open(sys.argv[2], "rb")
     rows = list(csv.DictReader(io.TextIOWrapper(f)))
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-    first = [i for i, r in enumerate(rows) if "stem_pack" in r["Kernel_Name"]]          # the step's first kernel
-    step = rows[first[-2]:first[-1]]
+    # one step = from the kernel after an optimizer group to the end of the next one, the step before the last group of the trace (as
+    # tools/step_timeline.py and tools/trace_summary.py cut it; the step no longer starts with a stem_pack launch)
+    groups = []
+    for i in (i for i, r in enumerate(rows) if "adamw" in r["Kernel_Name"]):
+        if not groups or i - groups[-1][-1] > 50:
+            groups.append([i])
+        else:
+            groups[-1].append(i)
+    step = rows[groups[-3][-1] + 1:groups[-2][-1] + 1]
     g = []
     for r in step:
         n, d = r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
@@ -36,7 +43,8 @@ def main():
         d = sum(g[pos:pos + c["kernels"]])
         pos += c["kernels"]
         p = c["problems"][0]
-        key = (p["family"], p["form"], p["M"], p["N"], p["K"], p["taps"], len(c["problems"]))
+        # (a 3x3 stride-2 data gradient by parity classes is listed with its MEAN reduction per row, K / 4: it shares M, N, K with the stride-1 form)
+        key = (p["family"], p["form"], p["M"], p["N"], p["K"] // 4 if p.get("s2") else p["K"], p["taps"], len(c["problems"]))
         a = agg.setdefault(key, [0, 0.0, 0.0, 0.0])
         a[0] += 1; a[1] += d; a[2] += sum(q["bytes"] for q in c["problems"]); a[3] += sum(q["flop"] for q in c["problems"])
     tot = sum(a[1] for a in agg.values())
