@@ -141,7 +141,7 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(GP p, const float* w
     if (p.scale) load8(p.scale + n, sc);
     if (p.shift) load8(p.shift + n, sh);
     const int64_t orow = p.c_rowmap ? (int64_t)p.c_rowmap[m] : (int64_t)m;
-    epilogue8<T>(p, v, sc, sh, m, orow, n);
+    epilogue_cols<T, 8>(p, v, sc, sh, m, orow, n);
 }
 
 template <int BM, int BN, int WGM, int WGN, int NST>
@@ -173,6 +173,8 @@ int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
     } else {
         CB_REQUIRE(!d->post_scale && !d->post_scale2, "cb_gemm: post_scale / post_scale2 need relu_bwd");
     }
+    // (no caller combines them, and the epilogue widths once disagreed on what the pair means: epilogue_cols applies one OR the other)
+    CB_REQUIRE(!(d->mask && d->gelu_grad_pre), "cb_gemm: mask and gelu_grad_pre exclude each other");
     p.batch = d->batch > 1 ? d->batch : 1;
     p.bs_a = d->batch_stride_a * esz; p.bs_b = d->batch_stride_b * esz;
     p.bs_c = d->batch_stride_c * (d->c_f32 ? 4 : esz); p.bs_r = d->batch_stride_rowsum;
@@ -216,7 +218,7 @@ int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
         p.wt = ok ? switches().wt : 0;
     }
     {   // specialised epilogue (FAST_EPI_COMBOS in gemm_impl.h): the call's option combination, if it is one of the listed ones and the
-        // row-contiguous bf16 write-through epilogue applies; CB_GEMM_FAST_EPI=0: the generic epilogue8 for everything
+        // row-contiguous bf16 write-through epilogue applies; CB_GEMM_FAST_EPI=0: the generic epilogue (epilogue_cols) for everything
         const bool fe_off = switches().fast_epi_off;
         p.fast_epi = 0;
         auto rows_ok = [&](const void* q, int64_t ld) { return q == nullptr || (ld % 8 == 0 && aligned16(q) && (int64_t)d->M * ld * 2 < 0x7fffffffll); };
@@ -234,8 +236,7 @@ int gemm_prepare(const cb_gemm_desc* d, Prepared& out) {
         }
         const bool plain = !wg_store && !fe_off && p.wt == 1 && p.batch == 1 && d->accumulate != 1 && p.alpha == 1.f && !d->zero_fill_pitch && !d->a_rowsum &&
                            d->N % 8 == 0 && d->ldc % 8 == 0 && aligned16(d->C) && (!d->shift || aligned16(d->shift)) && (!d->scale || aligned16(d->scale)) &&
-                           (d->res_rowmap ? (d->ldr % 8 == 0 && aligned16(d->residual)) : rows_ok(d->residual, d->ldr)) && rows_ok(d->mask, d->ldm) && rows_ok(d->gelu_grad_pre, d->ld_gelu) &&
-                           !(d->mask && d->gelu_grad_pre);
+                           (d->res_rowmap ? (d->ldr % 8 == 0 && aligned16(d->residual)) : rows_ok(d->residual, d->ldr)) && rows_ok(d->mask, d->ldm) && rows_ok(d->gelu_grad_pre, d->ld_gelu);
         if (plain && d->relu_bwd) {                                          // (validated above: mask, no scale / shift / act / dropout / relu_after)
             const bool ok = d->C2 && d->post_scale && d->ldc2 % 8 == 0 && aligned16(d->C2) && (int64_t)d->M * d->ldc2 * 2 < 0xffffffffll;
             const int flags = EF_RBWD | (d->residual ? EF_RES : 0) | (d->post_scale2 ? EF_PS2 : 0) | (d->res_rowmap ? EF_RMAP : 0) | (d->dgrad_s2 ? EF_CMAP : 0);

@@ -192,10 +192,10 @@ template <int ROWS, int KMODE> struct KrowDma8 {
 
 // ---------------------------------------------------------------------------------------------
 // Epilogue for a WGM x WGN grid of 8 waves.  The fp32 accumulators pass through LDS 64 tile rows at a time so that a thread owns
-// 8 consecutive columns of one row (16-byte, line-contiguous global accesses), then either the full cb_gemm epilogue (epilogue8)
+// 8 consecutive columns of one row (16-byte, line-contiguous global accesses), then either the full cb_gemm epilogue (epilogue_cols)
 // or -- K-split partial products -- plain fp32 stores into this split's slab of the workspace.
 // ---------------------------------------------------------------------------------------------
-// Code size (round 5, profiles/r05a_stamps.md): the epilogue8 body is ~10 KB of branchy straight-line code (every epilogue option is a
+// Code size (round 5, profiles/r05a_stamps.md): the generic epilogue body is ~10 KB of branchy straight-line code (every epilogue option is a
 // wave-uniform runtime branch).  Fully unrolled -- BM / PR passes x ITER chunks = 8 copies -- the epilogue was 78 KB that each workgroup
 // executes ONCE, i.e. entirely out of instruction-cache misses: ~1.1 us per chunk, 9 us for a bias-only 128x256 tile, 17 us for FFN1's
 // GELU + two outputs (longer than its 11 us K loop).  The pass loop and the chunk loop are therefore ROLLED: one copy of the body, warm
@@ -210,7 +210,7 @@ __device__ __forceinline__ void tile_epilogue8w(GP& p, f32x4 (&acc)[BM / WGM / 1
         // profiles/r06u_tile5_epilogue_bodies.txt; the metric step has no such launch, the inference row does.  Its weight-gradient
         // instantiation holds one body only, the fp32 store with the norm share.)
         if constexpr (!(BM == 256 && BN == 256) || WG)
-        if (!slab && p.fast_epi != 0 && (WG == (p.fast_epi == FAST_EPI_F32)) && fe_in_form(p.fast_epi, FORM)) {                         // specialised body for this call's option combination (gemm_impl.h fast_epilogue)
+        if (!slab && p.fast_epi != 0 && (WG == (p.fast_epi == FAST_EPI_F32)) && fe_in_form(p.fast_epi, FORM)) {                         // specialised body for this call's option combination (gemm_epilogue.h fast_epilogue)
             constexpr int WM_ = BM / WGM, WN_ = BN / WGN, FN_ = WN_ / 16, SROW_ = BN * 4 + 16, SUB_ = WM_ / PR;
             static_assert(WM_ % PR == 0 && PR * SROW_ <= SMEM_BYTES, "epilogue staging");
             const int lane_ = tid & 63, wave_ = tid >> 6;
@@ -280,7 +280,7 @@ __device__ __forceinline__ void tile_epilogue8w(GP& p, f32x4 (&acc)[BM / WGM / 1
                     store8(slab + (int64_t)m * p.N + n, v);
                 } else {
                     const int64_t orow = p.c_rowmap ? (int64_t)p.c_rowmap[m] : (int64_t)m;
-                    epilogue8<T>(p, v, sc, sh, m, orow, n);
+                    epilogue_cols<T, 8>(p, v, sc, sh, m, orow, n);
                 }
             }
         }

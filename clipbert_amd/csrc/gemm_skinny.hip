@@ -4,7 +4,7 @@
 // wave w takes the 32-deep K steps w, w+4, ..., every MFMA operand of up to six steps is requested at once straight from global memory in
 // fragment layout (A and a k-contiguous B: 16 bytes per lane, no LDS; a reduction-major B: its natural [k][64 columns] lines, staged in
 // the wave's own LDS slots and read back with the transpose read), and the four partial tiles meet in LDS, where each thread then
-// owns 8 consecutive columns of a row and runs the library's generic epilogue (epilogue_vec / epilogue_elem: every option of the
+// owns 8 consecutive columns of a row and runs the library's generic epilogue (epilogue_cols at width 4, or 1 at a ragged edge: every option of the
 // descriptor means what it means everywhere else).  The sum order differs from the other structures' (4 interleaved partial sums).
 #include "gemm_impl.h"
 
@@ -123,14 +123,21 @@ __global__ void __launch_bounds__(256) gemm_skinny_kernel(GP p, int a_vec, int b
     const int m = m0 + row, n = n0 + c8;
     if (m >= p.M || n >= p.N) return;
     const int64_t orow = p.c_rowmap ? (int64_t)p.c_rowmap[m] : (int64_t)m;
+    const float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
     if (p.c_vec && n + 8 <= p.N) {
-        epilogue_vec<bf16>(p, v0, m, orow, n);
-        epilogue_vec<bf16>(p, v1, m, orow, n + 4);
+#pragma unroll
+        for (int e = 0; e < 8; e += 4) {
+            float v[4] = {x[e], x[e + 1], x[e + 2], x[e + 3]}, sc[4], sh[4];
+            load_scale_shift(p, n + e, sc, sh);
+            epilogue_cols<bf16, 4>(p, v, sc, sh, m, orow, n + e);
+        }
     } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (n + e < p.N) epilogue_elem<bf16>(p, v0[e], m, orow, n + e);
-            if (n + 4 + e < p.N) epilogue_elem<bf16>(p, v1[e], m, orow, n + 4 + e);
+        for (int e = 0; e < 8; ++e) {
+            if (n + e >= p.N) break;
+            float v[1] = {x[e]}, sc[1], sh[1];
+            load_scale_shift(p, n + e, sc, sh);
+            epilogue_cols<bf16, 1>(p, v, sc, sh, m, orow, n + e);
         }
     }
 }

@@ -22,7 +22,7 @@
 // stores and residual reads are runs of BN * 2 bytes per row over BM consecutive rows.
 //
 // Waves 2 x 2; accumulators pass through a 16-row LDS staging buffer so that every thread owns 8 consecutive columns of a row
-// (16-byte accesses; the same epilogue8 as every other cb_gemm kernel: results are bit-identical to the 4-wave kernels, whose K loop
+// (16-byte accesses; the same epilogue_cols as every other cb_gemm kernel: results are bit-identical to the 4-wave kernels, whose K loop
 // adds the same K tiles in the same order).  Forward form only (A, B both k-contiguous).
 #pragma once
 #include "gemm_impl.h"
@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(256, OCC) gemm_stream_kernel(GP p) {
         }
 
         // ---- epilogue: 16 rows per pass through the staging buffer
-        // (rolled loops, round 5: one copy of the ~10 KB epilogue8 body that stays in the instruction cache across passes AND tiles;
+        // (rolled loops, round 5: one copy of the ~10 KB generic epilogue body that stays in the instruction cache across passes AND tiles;
         // unrolled, the NPASS x ITER copies made the per-tile loop larger than the cache, so every tile ran out of instruction misses)
         unsigned char* stg = smem + OFF_STG;
 #pragma unroll 1
@@ -170,8 +170,8 @@ __global__ void __launch_bounds__(256, OCC) gemm_stream_kernel(GP p) {
                 if (id < 16 * CPR && m < p.M) {
                     float v[8];
                     load8(reinterpret_cast<const float*>(stg + rl * SROW + cc * 32), v);
-                    if constexpr (EPI == 0) epilogue8<T>(p, v, sc, sh, m, (int64_t)m, n);
-                    else epilogue8<T, 2>(p, v, sc, sh, m, (int64_t)m, n, rp);
+                    if constexpr (EPI == 0) epilogue_cols<T, 8>(p, v, sc, sh, m, (int64_t)m, n);
+                    else epilogue_cols<T, 8, 2>(p, v, sc, sh, m, (int64_t)m, n, rp);
                 }
             }
         }

@@ -84,7 +84,8 @@ typedef struct {
                                * with ZEROS -- data gradient of a stride-2 1x1 convolution: output pixel m owns a 2x2 patch
                                * of input pixels of which only the first receives a value (pitch = input row width W);
                                * needs 16-byte-aligned 8-column chunks (N, ldc % 8 == 0)                             */
-    const void* mask; int64_t ldm;        /* optional: result zeroed where mask[m,n] <= 0 (ReLU bwd)  */
+    const void* mask; int64_t ldm;        /* optional: result zeroed where mask[m,n] <= 0 (ReLU bwd); not together with
+                                             gelu_grad_pre (an error) */
     void* C2; int64_t ldc2;   /* optional second output: value BEFORE act (GELU backward needs it)   */
     float alpha;              /* multiplies the accumulator first (1.0 if 0)                         */
     float dropout_p;          /* > 0: inverted dropout on the value before the residual add          */
@@ -108,7 +109,8 @@ typedef struct {
                                  buffer loads (fast path); otherwise element-wise guarded loads.           */
     const void* gelu_grad_pre; int64_t ld_gelu;  /* optional: result *= gelu'(pre[m,n]) (last step before the store):
                                  the GELU backward of BertIntermediate fused into the dgrad of BertOutput.dense;
-                                 with act == CB_ACT_SAVED_GRAD the tensor already holds gelu'(pre): result *= it  */
+                                 with act == CB_ACT_SAVED_GRAD the tensor already holds gelu'(pre): result *= it.
+                                 Not together with mask (an error).  */
     float* a_rowsum;          /* optional, weight-gradient form only (A and B CB_KROW): a_rowsum[m] += sum_k A(m,k),
                                  i.e. the bias gradient colsum(dY), computed on the matrix core next to dW (atomics) */
     int32_t batch;            /* > 1: `batch` independent problems of this shape in ONE launch (grid z); problem b uses

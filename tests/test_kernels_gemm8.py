@@ -115,7 +115,7 @@ def test_epilogue_dropout_against_restated_mask(hw, tile, M, N, K, split):
 def test_training_epilogue_dropout_against_restated_mask(hw, tile, N):
     """What BertSelfOutput / BertOutput launch in bf16 training: bias + dropout + residual with NO activation, contiguous aligned bf16
     output and residual -- the option combination with a specialised epilogue body (gemm_impl.h FAST_EPI_COMBOS[4]; the tanh of the case
-    above goes through the generic epilogue8 instead).  (x W^T + b) * m + residual against fp64 with the restated mask; with an all-zero
+    above goes through the generic epilogue_cols instead).  (x W^T + b) * m + residual against fp64 with the restated mask; with an all-zero
     residual the call stays on that combination and the non-zero outputs are the restated keep mask exactly."""
     M, K, p, seed, word = 300, 104, 0.3, 29, 123456789
     sp = torch.tensor([word], dtype=torch.int64, device=hw.dev)
@@ -308,7 +308,7 @@ def test_lazy_dma_emulation():
 def test_inference_gelu_body_equals_the_generic_epilogue_bit_for_bit(hw):
     """round 6: bias + GELU WITHOUT the stored derivative (BertIntermediate in inference) has a specialised epilogue body (combination 17)
     on the 128x256 / 256x128 8-wave tiles and the 4-wave tiles; the 256x256 forward kernel carries no specialised bodies (generic
-    epilogue8).  Same packed GELU everywhere: all five tiles agree bit for bit, and with PyTorch within the bf16 bound."""
+    epilogue_cols).  Same packed GELU everywhere: all five tiles agree bit for bit, and with PyTorch within the bf16 bound."""
     M, N, K = 300, 264, 64 * 3 + 8
     x, w, b = hw(rnd(M, K, seed=1).to(BF)), hw(rnd(N, K, seed=2, scale=0.1).to(BF)), hw(rnd(N, seed=3))
     ref = F.gelu(x.float() @ w.float().t() + b)

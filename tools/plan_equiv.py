@@ -96,6 +96,8 @@ def corpus(n_random, seed):
         for field, ld, prob in (("C2", "ldc2", 0.06), ("residual", "ldr", 0.08), ("mask", "ldm", 0.06), ("gelu_grad_pre", "ld_gelu", 0.05)):
             if some(prob):
                 kw[field], kw[ld] = PTR + (2 if some(0.1) else 0), N + (1 if some(0.1) else 0)
+        if "mask" in kw and "gelu_grad_pre" in kw:                        # (refused together since the widths of the epilogue became one function)
+            del kw["gelu_grad_pre"], kw["ld_gelu"]
         plain_wgrad = (a_mode, b_mode) == (2, 2)                          # (row sums / norm shares: mostly where gemm_prepare admits them)
         for field, prob in (("shift", 0.15), ("scale", 0.1), ("a_rowsum", 0.15 if plain_wgrad else 0.01), ("c_rowmap", 0.03),
                             ("sq_slots", 0.25 if wgrad and kw["accumulate"] != 1 else 0.01)):
