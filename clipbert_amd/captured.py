@@ -13,7 +13,8 @@ capture that raises has applied no part of a step -- parameters, moments and gra
 back, and the step bookkeeping it touched (lazy zero-grad flags, pending-node counts) is reset by the eager step that follows anyway; the
 signature is marked uncapturable.  From the third
 sight on: stage, ``set_learning_rates`` + ``optimizer.prepare_step()`` eagerly (fresh host-side hyper-parameters), ``graph.replay()``
-(fresh dropout masks: the graph advances the device seed word).  The cache is LRU over ``max_graphs`` entries; an evicted signature is
+(fresh dropout masks and, with the model config's pixel_sampling = "device", a fresh pixel selection: the graph advances the device seed
+word).  The cache is LRU over ``max_graphs`` entries; an evicted signature is
 captured again at its next sight and its static buffers go with its graph.
 
 Nothing is silently frozen into a graph: whatever produces per-step values on the host, or takes its launch geometry from the data,
@@ -178,7 +179,7 @@ class CapturedStep(_Replayer):
 
     Signature: dtype, shape and device of every tensor of the batch and which optional keys are present; tuple(n_examples_list);
     cfg.train_n_clips, num_frm, score_agg_func, task, num_labels; model.training; for pretraining cfg.mlm_rows, mlm_capacity, use_mlm,
-    use_itm; fold_clips.
+    use_itm; fold_clips; pixel_sampling and pixel_random_sampling_size of the config the encoder reads.
 
     ``pad_text_to`` (e.g. cfg.max_txt_len): text_input_ids / text_input_mask (and mlm_labels, with -100) are right-padded to that many
     columns with pad id 0 and mask 0 before the signature is taken, so that the text length of a batch stops multiplying signatures
@@ -188,7 +189,8 @@ class CapturedStep(_Replayer):
 
     Runs eagerly, with one warning per signature: a gradient exchange (``sync`` with several ranks or its loopback),
     cfg.gradient_accumulation_steps > 1, a data.RawFrames batch (its launch geometry comes from the host table), config.
-    pixel_random_sampling_size > 0 in training (numpy draws the selection per forward), the labelled-rows masked-LM head without a fixed
+    pixel_random_sampling_size > 0 in training with pixel_sampling = "host" (numpy draws the selection per forward; "device" draws it
+    inside the graph with cb_pixel_sample, seeded like the dropout masks), the labelled-rows masked-LM head without a fixed
     cfg.mlm_capacity, non-tensor batch entries the model reads, batch tensors that are not on the model's device (a loader that left them
     on the host), and a signature whose capture raised."""
 
@@ -201,13 +203,18 @@ class CapturedStep(_Replayer):
         return self.model.rt.bank.device
 
     # ---- what fixes the launch sequence -----------------------------------------------------------------------------------------
+    def _encoder_config(self):
+        """the config object the encoder reads (pixel sub-sampling keys)"""
+        return getattr(getattr(self.model.transformer, "bert", None), "config", self.model.config)
+
     def signature(self, batch):
         from .tasks import _get
-        cfg = self.cfg
+        cfg, enc_cfg = self.cfg, self._encoder_config()
         entries = tuple(sorted((k, _describe(v)) for k, v in batch.items() if k != "n_examples_list"))
         return (entries, tuple(batch["n_examples_list"]), _get(cfg, "train_n_clips", 1), _get(cfg, "num_frm"), _get(cfg, "score_agg_func", "mean"),
                 _get(cfg, "task"), _get(cfg, "num_labels"), bool(self.model.training), _get(cfg, "mlm_rows", "labelled"), _get(cfg, "mlm_capacity"),
-                _get(cfg, "use_mlm", True), _get(cfg, "use_itm", True), bool(self.fold_clips))
+                _get(cfg, "use_mlm", True), _get(cfg, "use_itm", True), bool(self.fold_clips),
+                getattr(enc_cfg, "pixel_sampling", "host") or "host", int(getattr(enc_cfg, "pixel_random_sampling_size", 0) or 0))
 
     def _why_eager(self, batch):
         from .data import RawFrames
@@ -219,9 +226,10 @@ class CapturedStep(_Replayer):
             return "gradient_accumulation_steps > 1"
         if isinstance(batch.get("visual_inputs"), RawFrames):
             return "RawFrames batch (launch geometry from its host table)"
-        enc_cfg = getattr(getattr(self.model.transformer, "bert", None), "config", self.model.config)          # (the object the encoder reads)
-        if self.model.training and int(getattr(enc_cfg, "pixel_random_sampling_size", 0) or 0) > 0:
-            return "pixel_random_sampling_size > 0 (the selection is drawn on the host per forward)"
+        enc_cfg = self._encoder_config()
+        if (self.model.training and int(getattr(enc_cfg, "pixel_random_sampling_size", 0) or 0) > 0
+                and (getattr(enc_cfg, "pixel_sampling", "host") or "host") != "device"):
+            return "pixel_random_sampling_size > 0 (the selection is drawn on the host per forward; pixel_sampling = 'device' draws it in the graph)"
         if batch.get("mlm_labels") is not None and _get(cfg, "mlm_rows", "labelled") == "labelled" and _get(cfg, "mlm_capacity") is None:
             return "labelled-rows masked-LM head without a fixed mlm_capacity"
         for k, v in batch.items():

@@ -49,7 +49,7 @@ SHARED_DEFAULTS = dict(
     cnn_lr_decay="linear", cnn_step_decay_epochs=None, freeze_cnn=0, inference_batch_size=64, inference_n_clips=1,
     e2e_weights_path=None, detectron2_weights_path=None, bert_weights_path=None, detectron2_model_cfg="", model_config=None, seed=42)
 TASK_DEFAULTS = {
-    "pretraining": dict(pixel_random_sampling_size=0, use_itm=1, use_mlm=1),
+    "pretraining": dict(pixel_random_sampling_size=0, pixel_sampling="host", use_itm=1, use_mlm=1),
     "video_retrieval": dict(itm_neg_size=1, classifier="mlp", cls_hidden_scale=2, margin=0.2, loss_type="ce"),
     "video_qa": dict(classifier="mlp", cls_hidden_scale=2, loss_type="ce", task="action"),
     "vqa": dict(classifier="mlp", cls_hidden_scale=2, loss_type="bce", num_labels=3129),
@@ -78,13 +78,14 @@ def load_task_config(path: str, task: str = "video_retrieval", **overrides) -> C
 
 def build_model_config(cfg: Config, config_root: Optional[str] = None) -> Config:
     """BertConfig(**load_json(cfg.model_config)) + the downstream keys (run_video_retrieval.py:184-193,
-    run_video_qa.py: same list, run_pretrain.py: pixel_random_sampling_size)."""
+    run_video_qa.py: same list, run_pretrain.py: pixel_random_sampling_size) and this project's pixel_sampling ("host": numpy draws the
+    selection as the reference does, "device": cb_pixel_sample does, which a captured step needs)."""
     path = cfg.model_config
     if config_root is not None and not os.path.isabs(path):
         path = os.path.join(config_root, path)
     with open(path) as fh:
         mc = Config(json.load(fh))
-    for k in ("num_labels", "classifier", "cls_hidden_scale", "loss_type", "margin", "pixel_random_sampling_size"):
+    for k in ("num_labels", "classifier", "cls_hidden_scale", "loss_type", "margin", "pixel_random_sampling_size", "pixel_sampling"):
         if k in cfg and cfg[k] is not None:
             mc[k] = cfg[k]
     return mc

@@ -10,7 +10,7 @@ from torch import nn
 from .. import ops
 from ..ops import ACT_GELU, ACT_TANH, KROW
 from .modules import BertEmbeddings, BertEncoder, BertPooler, VisualInputEmbedding, _cfg_get, as_config
-from .runtime import _SITE_ATTN, _SITE_EMB, _SITE_OUT, _SITE_POOL, _SITE_SELF_OUT, Runtime, _pick_split, _seed
+from .runtime import _SITE_ATTN, _SITE_EMB, _SITE_OUT, _SITE_PIXEL, _SITE_POOL, _SITE_SELF_OUT, Runtime, _pick_split, _seed
 
 
 class ClipBertBaseModel(nn.Module):
@@ -56,19 +56,26 @@ def encoder_forward(model: ClipBertBaseModel, grid, ids, mask, src_row, pooled_d
     training = model.training
     p_h = _drop_p(model, training)
     p_a = _drop_p(model, training, "attention_probs_dropout_prob")
-    fwd_i = 0
-    if p_h > 0 or p_a > 0:                    # every training forward draws its own dropout masks (the reference's
-        fwd_i = rt.forward_count              # nn.Dropout does); the backward regenerates them from pack.fwd_i
-        rt.forward_count += 1
     bsz, lt = ids.shape[0] * text_repeat, ids.shape[1]
     bv, t, hg, wg, _ = grid.shape
-    # optional random pixel sub-sampling: training phase of pre-training only (modeling.py:80-88)
-    sel = None
     lv = hg * wg
     nsamp = int(_cfg_get(cfg, "pixel_random_sampling_size", 0) or 0)
-    if nsamp > 0 and training and nsamp < lv:
-        idx = np.sort(np.random.choice(lv, size=nsamp, replace=False))     # numpy global RNG, as the reference
-        sel = torch.from_numpy(idx.astype(np.int32)).to(dev)
+    sampling = _cfg_get(cfg, "pixel_sampling", "host") or "host"
+    if sampling not in ("host", "device"):
+        raise ValueError(f"pixel_sampling must be 'host' or 'device', not {sampling!r}")
+    sample = nsamp > 0 and training and nsamp < lv
+    fwd_i = 0
+    if p_h > 0 or p_a > 0 or (sample and sampling == "device"):
+        fwd_i = rt.forward_count              # every training forward draws its own dropout masks (the reference's nn.Dropout does) and
+        rt.forward_count += 1                 # its own device-side pixel selection; the backward regenerates the masks from pack.fwd_i
+    # optional random pixel sub-sampling: training phase of pre-training only (modeling.py:80-88)
+    sel = None
+    if sample:
+        if sampling == "device":              # one launch, seeded like a dropout site: capturable, fresh per replay (cb_pixel_sample)
+            sel = ops.pixel_sample(lv, nsamp, _seed(_SITE_PIXEL, 0, fwd_i), rt.seed_dev, device=dev)
+        else:
+            idx = np.sort(np.random.choice(lv, size=nsamp, replace=False))     # numpy global RNG, as the reference
+            sel = torch.from_numpy(idx.astype(np.int32)).to(dev)
         lv = nsamp
     L = lt + lv
     M = bsz * L

@@ -46,8 +46,9 @@ class Runtime:
         self.pending_cnn_nodes = 0
         self.prepare_args = None                         # keyword arguments of the prepare() call that built this runtime
         self._ln_off = None                              # (bank, offsets of the encoder LayerNorm gradients): cache of _ln_offsets
-        self.forward_count = 0                           # host counter folded into every dropout seed: each forward (each
-                                                         # clip of a clip loop) draws its own masks; kept in the saved pack
+        self.forward_count = 0                           # host counter folded into every dropout seed (and the device-drawn pixel
+                                                         # selection's): each forward (each clip of a clip loop) draws its own
+                                                         # masks; kept in the saved pack
 
     # ---- step bookkeeping: each hook fires in the LAST pending backward of its kind ("encoder" | "cnn") ---------------------------
     def begin_step(self):
@@ -107,6 +108,7 @@ def _pick_split(mo, no, kred):
 
 # dropout sites -> distinct seed streams
 _SITE_EMB, _SITE_ATTN, _SITE_SELF_OUT, _SITE_OUT, _SITE_POOL, _SITE_REG = 1, 2, 3, 4, 5, 6
+_SITE_PIXEL = 7          # not a dropout: the pixel sub-sampling drawn on the device (ops.pixel_sample), a seed stream of its own
 
 
 def _seed(site, layer=0, fwd=0):

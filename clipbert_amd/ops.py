@@ -726,6 +726,22 @@ def dropout(x, p, seed=0, seed_ptr=None, out=None):
     return y
 
 
+def pixel_sample(lv: int, n: int, seed=0, seed_ptr=None, out=None, device=None):
+    """cb_pixel_sample: int32 (n,) -- a uniformly random n-subset of range(lv) in ascending order, drawn on the device from ``seed`` plus the
+    device word behind ``seed_ptr`` (the dropout convention).  One launch on the current stream of the output, no host sync: capturable.
+    ``out``: int32, contiguous, at least n elements (its first n are written); else a new tensor on ``device`` (default: seed_ptr's)."""
+    if out is None:
+        if device is None:
+            if seed_ptr is None:
+                raise ValueError("pixel_sample: pass out=, device= or seed_ptr=")
+            device = seed_ptr.device
+        out = torch.empty(max(int(n), 0), dtype=torch.int32, device=device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n, (out.dtype, out.shape, n)
+    assert seed_ptr is None or (seed_ptr.dtype == torch.int64 and seed_ptr.numel() == 1 and seed_ptr.device == out.device)
+    _chk(_lib.get().cb_pixel_sample(_ptr(out), lv, n, int(seed) % (1 << 64), _ptr(seed_ptr), _stream(out)), "cb_pixel_sample")
+    return out[:n] if out.numel() != n else out
+
+
 def elu_bn1d_fwd(x, gamma, beta, running_mean, running_var, training: bool, momentum: float = 0.1, eps: float = 1e-5, save: bool = False):
     """ELU + BatchNorm1d over the batch (ClipBertForRegression.regressor[1:3]); returns (y, save_mean, save_invstd)."""
     b, d = x.shape

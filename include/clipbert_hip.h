@@ -418,6 +418,18 @@ int cb_mlm_loss_fwd(const float* logits, int64_t ld, const int32_t* slot_row, co
 int cb_mlm_loss_bwd(int32_t dtype, const float* logits, int64_t ld, const float* lse, const int32_t* slot_row, const int64_t* slot_label,
                     int64_t ignore_index, const float* dloss_rows, void* dlogits, int64_t ldd, int32_t cap, int32_t V, void* stream);
 
+/* ---- random pixel sub-sampling, drawn on the device ----------------------------------------------------------------------------------
+ * The pre-training configuration keeps a random sorted subset of the visual tokens in every training forward
+ * (get_random_sample_indices: np.random.choice(replace=False) then sort, one selection shared by the batch; src/modeling/modeling.py:15-34,
+ * used at :80-88).  cb_pixel_sample draws it without the host: sel[0..n) = a uniformly random n-subset of {0..Lv-1} in ASCENDING order,
+ * defined exactly (tests/pixel_sample_restatement.py restates it):
+ *   s = seed + (seed_ptr ? *seed_ptr : 0) mod 2^64 (the convention of every dropout site: the device word advances inside a captured step);
+ *   key_i = (hash(s, i) & ~0xFFFF) | i, hash = the splitmix64 finaliser of the dropout masks -- 48 random bits over the index, all distinct;
+ *   the selection = the n indices with the smallest keys (independent keys: every n-subset is equally likely).
+ * ONE launch of one workgroup, no host synchronisation, no scratch: capturable.  1 <= n <= Lv <= 65536 (n == Lv: 0..Lv-1); anything else,
+ * or a null sel, fails with a message and launches nothing.  sel is what cb_visual_embed_fwd / cb_visual_embed_bwd take. */
+int cb_pixel_sample(int32_t* sel, int32_t Lv, int32_t n, uint64_t seed, const uint64_t* seed_ptr, void* stream);
+
 /* ---- image-VQA head over SPARSE answers -----------------------------------------------------------------------------------------------
  * The VQA targets are at most ten (answer, score) pairs per question that ClipBertVQADataset._get_vqa_targets
  * (src/datasets/dataset_vqa.py:57-72) scatters into num_labels = 3129 zeros; here they stay sparse: ans_ids int32 / ans_scores fp32,
@@ -570,7 +582,8 @@ const char* cb_last_error(void);
  * 12 = cb_copy_ranges (batch staging for captured task loops; nothing else changed);
  * 13 = cb_vqa_loss_fwd, cb_vqa_loss_bwd (the image-VQA head over sparse answers; nothing else changed);
  * 14 = cb_gemm_desc grew by res_rowmap / res_rows / dgrad_s2 at its END (zero = off: the residual through a row map of its own and the
- *      3x3 stride-2 data gradient by parity classes -- the "tail form" of a bottleneck block whose consumer reads even pixels only) */
+ *      3x3 stride-2 data gradient by parity classes -- the "tail form" of a bottleneck block whose consumer reads even pixels only);
+ * 15 = cb_pixel_sample (the pre-training pixel sub-sampling drawn on the device; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
