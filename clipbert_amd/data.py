@@ -242,6 +242,37 @@ def vqa_dense_targets(ids: torch.Tensor, scores: torch.Tensor, num_labels: int) 
     return dense[:, :num_labels].contiguous()
 
 
+# ---- MSRVTT multiple-choice batches ----------------------------------------------------------------------------------------------
+def collate_mc(videos, option_ids, option_mask, question_ids, answers=None) -> Dict:
+    """The batch of MSRVTTMCCollator.collate_batch (src/datasets/dataset_video_retrieval.py:328-361) from already tokenised options --
+    for tasks.mc_clip_logits / inference_retrieval_mc.  ``videos``: B tensors (n_clips*num_frm, 3, H, W) of one shape (or the stacked
+    (B, ...) tensor); ``option_ids`` / ``option_mask``: per video the (n_options, L) token ids and attention mask of its candidate
+    captions (B tensors of one shape, or stacked (B, n_options, L), or already flat (B*n_options, L)); ``question_ids``: one id per
+    video.  Returns visual_inputs (B, n_clips*num_frm, 3, H, W), text_input_ids / text_input_mask (B*n_options, L) -- video v's options
+    are rows v*n_options .. --, question_ids, labels None and n_examples_list [1]*B; the reference's ``meta`` (the option strings) is
+    omitted.  ``answers`` (the index of each video's right option) is passed through as batch["answers"]: with the question ids it is
+    what the ``id2answer`` of tasks.inference_retrieval_mc is made of."""
+    vis = videos if torch.is_tensor(videos) else torch.stack(list(videos))
+    bsz = vis.shape[0]
+    question_ids = list(question_ids)
+
+    def flat(x):
+        x = x if torch.is_tensor(x) else torch.stack(list(x))
+        return x.reshape(-1, x.shape[-1]) if x.dim() == 3 else x
+
+    ids, mask = flat(option_ids), flat(option_mask)
+    if len(question_ids) != bsz or ids.dim() != 2 or ids.shape != mask.shape or ids.shape[0] % max(bsz, 1) != 0:
+        raise ValueError(f"collate_mc: {bsz} videos, {len(question_ids)} question ids, option ids {tuple(ids.shape)}, mask {tuple(mask.shape)}")
+    batch = dict(visual_inputs=vis, text_input_ids=ids, text_input_mask=mask, question_ids=question_ids, labels=None,
+                 n_examples_list=[1] * bsz)
+    if answers is not None:
+        answers = [int(a) for a in answers]
+        if len(answers) != bsz:
+            raise ValueError(f"collate_mc: {len(answers)} answers for {bsz} videos")
+        batch["answers"] = answers
+    return batch
+
+
 class InfiniteIterator:
     """iterate an iterable object infinitely (src/datasets/dataloader.py:155-175)"""
     def __init__(self, iterable):

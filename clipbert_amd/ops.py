@@ -649,6 +649,28 @@ def retrieval_scores(logits) -> torch.Tensor:
     return out
 
 
+def mc_predict(stack: torch.Tensor, n_options: int, mode: int, clip_stride: Optional[int] = None):
+    """cb_mc_predict on the fp32 stack (n_clips, R, C) of per-clip logits, R = n_q * n_options rows, C = 1 | 2; each clip contiguous, the
+    dim-0 stride may exceed R * C (a view of a padded buffer; ``clip_stride`` overrides it, in elements) -> (scores fp32 (R,): the row's
+    probability after pooling the clips with ``mode`` (AGG_MEAN | AGG_MAX | AGG_LSE); pred int32 (n_q,): the arg-max over each group of
+    ``n_options`` rows).  One launch, no host synchronisation."""
+    if stack.dim() != 3 or stack.dtype != torch.float32:
+        raise ValueError(f"mc_predict: expected an fp32 (n_clips, rows, C) stack, got {stack.dtype} {tuple(stack.shape)}")
+    n_clips, rows, c = stack.shape
+    n_options = int(n_options)
+    if n_options < 1 or rows % n_options != 0:
+        raise ValueError(f"mc_predict: {rows} rows are not a multiple of n_options = {n_options}")
+    if rows * c > 1 and not stack[0].is_contiguous():
+        raise ValueError("mc_predict: each clip's (rows, C) logits must be contiguous")
+    if clip_stride is None:
+        clip_stride = stack.stride(0) if n_clips > 1 else max(stack.stride(0), rows * c)
+    scores = torch.empty(rows, dtype=torch.float32, device=stack.device)
+    pred = torch.empty(rows // n_options, dtype=torch.int32, device=stack.device)
+    _chk(_lib.get().cb_mc_predict(_ptr(stack), int(clip_stride), n_clips, rows // n_options, n_options, c, int(mode), _ptr(scores), _ptr(pred),
+                                  _stream(stack)), "cb_mc_predict")
+    return scores, pred
+
+
 def colsum(g, out, m=None, n=None, ldg=None):
     """out[n] += sum_m g[m, n] (fp32 atomics)."""
     m = g.shape[0] if m is None else m

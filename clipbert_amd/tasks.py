@@ -12,7 +12,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import clips
+from . import clips, ops
 from .optim import get_lr_sched
 
 
@@ -557,6 +557,144 @@ def inference_retrieval(model, videos, cfg, gt_txt_id2vid_id: Optional[Dict] = N
     metrics = eval_retrieval(rows, gt_txt_id2vid_id) if gt_txt_id2vid_id is not None else None
     model.train(was_training)
     return rows, metrics
+
+
+# ---- MSRVTT multiple-choice test (run_msrvtt_mc.py:136-243) ----------------------------------------------------------------
+_AGG_MODES = {"mean": ops.AGG_MEAN, "max": ops.AGG_MAX, "lse": ops.AGG_LSE}
+
+
+def _agg_mode(pool_method: str) -> int:
+    if pool_method not in _AGG_MODES:                       # (the runner raises ValueError too, :186-188)
+        raise ValueError(f"cfg.score_agg_func must be one of {sorted(_AGG_MODES)}, not {pool_method!r}")
+    return _AGG_MODES[pool_method]
+
+
+@torch.no_grad()
+def mc_clip_logits(model, batch: Dict, cfg, n_options: int = 5, cache_cnn: bool = True, max_pairs_per_pass: int = 256,
+                   capture=None) -> torch.Tensor:
+    """The clip loop of the multiple-choice test (:165-178) -> the fp32 (inference_n_clips, B*n_options, C) stack of per-clip logits, on
+    the device.  ``batch`` has the keys of MSRVTTMCCollator (data.collate_mc): visual_inputs (B, n_clips*num_frm, 3, H, W),
+    text_input_ids / text_input_mask (B*n_options, L) -- video v's options are rows v*n_options .. -- and n_examples_list == [1]*B.
+
+    cache_cnn=False is the reference's order of evaluation: one full model(batch) per clip with n_examples_list multiplied by n_options
+    (forward_step, :136-142).  cache_cnn=True (default) runs ONE CNN batch over all B*n_clips clips and then only the cross-modal encoder,
+    over runs of (clip, video) blocks of n_options pairs each, at most ``max_pairs_per_pass`` pairs per pass (the reasoning and the
+    default of inference_retrieval_video); the passes walk the blocks clip-major, so their logits concatenate into the stack as they
+    come.  ``capture``: as in inference_retrieval_video -- None / False, True (the CapturedForward kept on the model), "dry", or a
+    CapturedForward; the encoder passes then replay from its graphs (one full and one remainder signature per batch shape).
+    cache_cnn=True only."""
+    if capture:
+        from .captured import CapturedForward
+        if not cache_cnn:
+            raise ValueError("mc_clip_logits(capture=...) replays the encoder passes over cached grid features: cache_cnn=True only")
+        if not isinstance(capture, CapturedForward):
+            if getattr(model, "_captured_forward", None) is None:
+                model._captured_forward = CapturedForward(model, mode="dry" if capture == "dry" else "graph")
+            capture = model._captured_forward
+    n_clips, num_frm, n_options = int(_get(cfg, "inference_n_clips", 1)), int(_get(cfg, "num_frm")), int(n_options)
+    vis, ids, mask = batch["visual_inputs"], batch["text_input_ids"], batch["text_input_mask"]
+    counts = list(batch["n_examples_list"])
+    bsz = len(counts)
+    if any(e != 1 for e in counts) or vis.shape[0] != bsz or ids.shape[0] != bsz * n_options:
+        raise ValueError(f"mc_clip_logits: expected one question of {n_options} options per video, got n_examples_list {counts}, "
+                         f"{vis.shape[0]} videos and {ids.shape[0]} text rows")
+    if not cache_cnn:
+        vis = vis.view(bsz, n_clips, num_frm, *vis.shape[2:])
+        per_clip = []
+        for c in range(n_clips):
+            mini = dict(visual_inputs=vis[:, c].contiguous() if n_clips > 1 else vis[:, 0], text_input_ids=ids, text_input_mask=mask,
+                        labels=None, n_examples_list=[e * n_options for e in counts])
+            per_clip.append(model(mini)["logits"])
+        return torch.stack(per_clip).float()
+    grid = model.grid_features(vis.view(bsz * n_clips, num_frm, *vis.shape[2:]))      # row v*n_clips + c: the plain view, no copy
+    if n_clips > 1 and bsz > 1:                                                         # clip-major blocks: row c*bsz + v
+        grid = grid.reshape(bsz, n_clips, *grid.shape[1:]).transpose(0, 1).reshape(bsz * n_clips, *grid.shape[1:])
+    ids3, mask3 = ids.view(bsz, n_options, -1), mask.view(bsz, n_options, -1)
+    n_blocks = n_clips * bsz
+    per_pass = max(1, int(max_pairs_per_pass) // n_options)                              # (clip, video) blocks per encoder pass
+    parts = []
+    for j0 in range(0, n_blocks, per_pass):
+        j1 = min(j0 + per_pass, n_blocks)
+        seg_ids, seg_mask, j = [], [], j0
+        while j < j1:                                                                   # the videos of blocks j0..j1-1: runs of v = j % bsz
+            v = j % bsz
+            take = min(bsz - v, j1 - j)
+            seg_ids.append(ids3[v:v + take])
+            seg_mask.append(mask3[v:v + take])
+            j += take
+        p_ids = (seg_ids[0] if len(seg_ids) == 1 else torch.cat(seg_ids)).reshape((j1 - j0) * n_options, -1)
+        p_mask = (seg_mask[0] if len(seg_mask) == 1 else torch.cat(seg_mask)).reshape((j1 - j0) * n_options, -1)
+        if capture:
+            lg = capture.logits(grid[j0:j1], p_ids, p_mask, [n_options] * (j1 - j0))
+        else:
+            lg = model.forward_from_grid(dict(visual_inputs=grid[j0:j1], text_input_ids=p_ids, text_input_mask=p_mask, labels=None,
+                                              n_examples_list=[n_options] * (j1 - j0)))["logits"]
+        parts.append(lg)
+    lg = parts[0] if len(parts) == 1 else torch.cat(parts)
+    return lg.float().reshape(n_clips, bsz * n_options, -1)
+
+
+@torch.no_grad()
+def mc_predict_batch(model, batch: Dict, cfg, n_options: int = 5, cache_cnn: bool = True, max_pairs_per_pass: int = 256, capture=None):
+    """(pred int32 (B,), scores fp32 (B*n_options,)) of one batch, both on the device: mc_clip_logits, then the pooling over the clips
+    (cfg.score_agg_func), the probability and the arg-max over each question's options in one launch (ops.mc_predict; :178-195).  No
+    host synchronisation."""
+    mode = _agg_mode(_get(cfg, "score_agg_func", "mean"))
+    stack = mc_clip_logits(model, batch, cfg, n_options=n_options, cache_cnn=cache_cnn, max_pairs_per_pass=max_pairs_per_pass, capture=capture)
+    scores, pred = ops.mc_predict(stack, n_options, mode)
+    return pred, scores
+
+
+def gather_mc_predictions(pred_id2ans: Dict, group=None) -> Dict:
+    """The {question id: predicted option} dicts of all ranks merged on every rank, in rank order -- the exchange the reference does
+    through per-rank JSON files on shared storage and merge_dicts (:202-234); here ONE all_gather_object.  A single process returns its
+    dict unchanged."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return pred_id2ans
+    parts = [None] * dist.get_world_size(group)
+    dist.all_gather_object(parts, (list(pred_id2ans.keys()), list(pred_id2ans.values())), group=group)
+    merged: Dict = {}
+    for keys, values in parts:
+        merged.update(zip(keys, values))
+    return merged
+
+
+def mc_accuracy(pred_id2ans: Dict, id2answer: Dict, force_same: bool = True) -> Dict[str, str]:
+    """ClipBertMSRVTTMCEvalDataset.evaluate_qa_accuracy (src/datasets/dataset_video_retrieval.py:307-325) on the ground-truth dict
+    instead of the dataset: with ``force_same`` the predictions must name exactly the ground truth's ids (asserted), without it every
+    predicted id is looked up.  Returns dict(mc_accuracy="<percent, 2 decimals>")."""
+    if force_same:
+        assert set(id2answer) == set(pred_id2ans), "the predictions and the ground truth name different question ids"
+    hits = np.asarray([int(id2answer[k]) == int(a) for k, a in pred_id2ans.items()], dtype=bool)
+    acc = np.mean(hits)                                     # (no predictions: nan, as the reference's mean of an empty array)
+    return dict(mc_accuracy=f"{100 * acc:.2f}")
+
+
+@torch.no_grad()
+def inference_retrieval_mc(model, val_loader, cfg, n_options: int = 5, id2answer: Optional[Dict] = None, group=None, cache_cnn: bool = True,
+                           capture=False):
+    """inference_retrieval_mc of the reference (:145-243) over the batches of THIS rank -> (pred_id2ans of all ranks, metrics or None).
+    ``val_loader`` yields the batches of data.collate_mc (``question_ids`` names each video's question; an ``answers`` entry is not
+    read).  The predictions stay on the device until the loader is exhausted: one concatenation and one .tolist() bring them to the
+    host.  ``id2answer`` ({question id: index of the right option}, of ALL ranks' questions) gives metrics = mc_accuracy(...);
+    ``capture``: handed to every mc_clip_logits (see there).  The model is put in eval mode for the loop and returned to its mode."""
+    was_training = model.training
+    model.eval()
+    qids: List = []
+    preds: List[torch.Tensor] = []
+    for batch in val_loader:
+        q = list(batch["question_ids"])
+        assert len(q) == len(batch["n_examples_list"]), (len(q), len(batch["n_examples_list"]))
+        pred, _scores = mc_predict_batch(model, batch, cfg, n_options=n_options, cache_cnn=cache_cnn, capture=capture or None)
+        qids.extend(q)
+        preds.append(pred)
+    answers = (preds[0] if len(preds) == 1 else torch.cat(preds)).tolist() if preds else []
+    pred_id2ans = {q: int(a) for q, a in zip(qids, answers)}
+    pred_id2ans = gather_mc_predictions(pred_id2ans, group)
+    metrics = mc_accuracy(pred_id2ans, id2answer, force_same=True) if id2answer is not None else None
+    model.train(was_training)
+    return pred_id2ans, metrics
 
 
 # ---- video QA inference (run_video_qa.py:216-300) ------------------------------------------------------------------------

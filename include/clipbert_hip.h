@@ -502,6 +502,16 @@ int cb_head_loss(int32_t kind, const float* x, const float* y, float* loss, cons
                  float margin, void* stream);
 /* Retrieval scores of the inference loop (src/tasks/run_video_retrieval.py:681-690): C == 2: softmax(logits)[:, 1]; C == 1: sigmoid. */
 int cb_retrieval_scores(const float* logits, float* out, int64_t rows, int32_t C, void* stream);
+/* Multiple-choice scoring of the MSRVTT MC test (src/tasks/run_msrvtt_mc.py:172-195: torch.stack of the per-clip logits, mean / max /
+ * logsumexp over the clips, softmax[:, 1] or sigmoid, view(-1, n_options).max(1)[1]) in ONE launch, no workspace.  logits: the fp32 stack,
+ * clip k, row r, class c at logits[k * clip_stride + r * C + c], r in [0, n_q * n_options), C = 1 | 2, clip_stride >= n_q * n_options * C
+ * (a padded stack, or one whose base is only 4-byte aligned, is legal).  mode: CB_AGG_MEAN | CB_AGG_MAX | CB_AGG_LSE (max-shifted).
+ * scores[r] (fp32, n_q * n_options) = sigmoid(pooled[r, 1] - pooled[r, 0]) = softmax(pooled[r])[1] for C == 2, sigmoid(pooled[r, 0]) for
+ * C == 1 -- not rounded (only the retrieval loop rounds its scores).  pred[q] (int32, n_q) = the index in [0, n_options) of the largest
+ * score of rows q * n_options ..: the lowest index among equals, a NaN larger than any number (torch.max).  Any n_options >= 1 and
+ * n_q >= 1: a question's options are reduced inside one wave. */
+int cb_mc_predict(const float* logits, int64_t clip_stride, int32_t n_clips, int32_t n_q, int32_t n_options, int32_t C, int32_t mode,
+                  float* scores, int32_t* pred, void* stream);
 /* Mean of n per-example losses (the runners' loss.mean(), run_video_retrieval.py:422) and its backward
  * dx[i] = *dmean / n; `*counter += inc` on a device word (the dropout seed word a captured step advances). */
 int cb_mean_fwd(const float* x, int64_t n, float* out, void* stream);
@@ -583,7 +593,8 @@ const char* cb_last_error(void);
  * 13 = cb_vqa_loss_fwd, cb_vqa_loss_bwd (the image-VQA head over sparse answers; nothing else changed);
  * 14 = cb_gemm_desc grew by res_rowmap / res_rows / dgrad_s2 at its END (zero = off: the residual through a row map of its own and the
  *      3x3 stride-2 data gradient by parity classes -- the "tail form" of a bottleneck block whose consumer reads even pixels only);
- * 15 = cb_pixel_sample (the pre-training pixel sub-sampling drawn on the device; nothing else changed) */
+ * 15 = cb_pixel_sample (the pre-training pixel sub-sampling drawn on the device; nothing else changed);
+ * 16 = cb_mc_predict (the MSRVTT multiple-choice scoring: pooling, probability and arg-max per question; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
