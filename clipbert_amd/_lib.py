@@ -18,6 +18,7 @@ ROWK, ROWK_GATHER, KROW, KROW_TAPS, KROW_GATHER = 0, 1, 2, 3, 4
 OPT_ADAMW, OPT_ADAM, OPT_ADAMAX = 0, 1, 2          # CB_OPT_*: the algo of cb_optim_step
 YUV_LAYOUTS = {"i420": 0, "nv12": 1}               # CB_YUV_I420 / CB_YUV_NV12: the layout of cb_resize_pack_yuv420
 YUV_MATRICES = {"bt601": 0, "bt601-full": 1, "bt709": 2, "bt709-full": 3}      # CB_YUV_BT*: its matrix
+PIXFMTS = {"rgb": 0, "i420": 1, "nv12": 2}         # CB_PIXFMT_*: how cb_resize_table_check counts a frame's bytes
 
 vp, i32, i64, f32, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint64
 
@@ -57,6 +58,9 @@ _SIGNATURES = {
     "cb_stem_pack": [i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "cb_resize_pack_u8": [i32, vp, i64, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp],
     "cb_resize_pack_yuv420": [i32, vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp],
+    "cb_resize_pack_u8_src": [i32, vp, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp],
+    "cb_resize_pack_yuv420_src": [i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp],
+    "cb_resize_table_check": [vp, i32, i64, i32, i32],
     "cb_image_norm": [vp, vp, vp, vp, i64, i64, vp],
     "cb_maxpool_fwd": [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "cb_maxpool2_bwd": [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],

@@ -106,6 +106,13 @@ class _Replayer:
         """the caller's tensors (on the buffers' device: anything else runs eagerly) into the static buffers, ONE launch"""
         ops.copy_ranges([(buf, tensors[k].contiguous()) for k, buf in bufs.items()])
 
+    def _static(self, others, bufs):
+        """(what the captured body is handed, the entry's data.FrameSource or None)"""
+        return dict(others, **bufs), None
+
+    def _stage_entry(self, entry, tensors):
+        self._stage(entry.bufs, tensors)
+
     def _off_device(self, tensors):
         """the fallback reason for a tensor that is not where the model is (a graph would run it elsewhere than the eager step does)"""
         dev = self._device()
@@ -125,7 +132,7 @@ class _Replayer:
         entry = self.graphs.get(sig)
         if entry is not None:
             self.graphs.move_to_end(sig)
-            self._stage(entry.bufs, tensors)
+            self._stage_entry(entry, tensors)
             out = self._replay(entry)
             self.stats["replays"] += 1
             self.log.append("replay")
@@ -142,9 +149,9 @@ class _Replayer:
     def _capture(self, sig, tensors, others):
         dev = self._device()
         bufs = {k: torch.empty(v.shape, dtype=v.dtype, device=dev) for k, v in tensors.items()}
-        static = dict(others, **bufs)
-        self._stage(bufs, tensors)
-        entry = SimpleNamespace(graph=None, bufs=bufs, static=static, out=None, body=self._body(static))
+        static, source = self._static(others, bufs)
+        entry = SimpleNamespace(graph=None, bufs=bufs, static=static, source=source, out=None, body=self._body(static))
+        self._stage_entry(entry, tensors)
         if self.mode == "graph":
             if self._pool is None:
                 self._pool = torch.cuda.graph_pool_handle()
@@ -187,17 +194,35 @@ class CapturedStep(_Replayer):
     attention, so results then differ from the un-padded eager step only by the order of the floating-point sums in attention (its
     key tiles shift); eager sights and fallbacks run on the padded batch too.
 
+    ``raw_frames=True`` (tasks.start_training: cfg.capture_raw_frames): data.RawFrames batches replay too.  Such an entry contributes
+    its leading shape, max_img_size, hwc, pixfmt, matrix and device to the signature -- NOT its byte count or any table value: batches of
+    other native resolutions replay from the same graph.  Per signature the static state is an (n_frames, 5) table buffer, filled by the
+    staging launch of the text tensors, and one descriptor (data.FrameSource: a pinned two-slot upload guarded by events, never
+    captured); the captured body sees the indirect RawFrames over the two, whose launches (cb_resize_pack_u8_src / _yuv420_src) read
+    address and size of the batch's ``flat`` from the descriptor: the pixel bytes are read where the loader put them, never copied.
+    Every step, replays included, first runs ops.resize_table_check on the batch's host table against the batch's own byte count and
+    raises what the eager step's launch would have raised -- before anything is staged or replayed.  The stepper holds the staged
+    batch's ``flat`` until the next batch of that signature has been staged (or the entry is evicted); descriptor upload, staging and
+    replay are ordered on the current stream.  ``mode="dry"`` does the same and runs the eager step on the indirect RawFrames.
+
     Runs eagerly, with one warning per signature: a gradient exchange (``sync`` with several ranks or its loopback),
-    cfg.gradient_accumulation_steps > 1, a data.RawFrames batch (its launch geometry comes from the host table), config.
+    cfg.gradient_accumulation_steps > 1, a data.RawFrames batch without ``raw_frames=True`` (nothing re-points a graph's frozen buffer
+    argument), and with it: one without a host table (its rows could not be checked before a replay), one whose ``flat`` or ``table``
+    is not on the model's device, one that is indirect already; config.
     pixel_random_sampling_size > 0 in training with pixel_sampling = "host" (numpy draws the selection per forward; "device" draws it
     inside the graph with cb_pixel_sample, seeded like the dropout masks), the labelled-rows masked-LM head without a fixed
     cfg.mlm_capacity, non-tensor batch entries the model reads, batch tensors that are not on the model's device (a loader that left them
     on the host), and a signature whose capture raised."""
 
-    def __init__(self, model, optimizer, cfg, loss_fn=None, fold_clips=True, max_graphs=8, pad_text_to=None, sync=None, mode="graph"):
+    RAW_TABLE = "visual_inputs.table"              # the key of a RawFrames batch's table among the staged tensors
+
+    def __init__(self, model, optimizer, cfg, loss_fn=None, fold_clips=True, max_graphs=8, pad_text_to=None, sync=None, mode="graph",
+                 raw_frames=False):
         super().__init__(max_graphs, mode)
         self.model, self.optimizer, self.cfg, self.loss_fn, self.fold_clips, self.sync = model, optimizer, cfg, loss_fn, fold_clips, sync
         self.pad_text_to = int(pad_text_to) if pad_text_to else None
+        self.raw_frames = bool(raw_frames)
+        self._raw = None                            # the RawFrames of the batch being stepped, when it takes the replay path
 
     def _device(self):
         return self.model.rt.bank.device
@@ -210,11 +235,26 @@ class CapturedStep(_Replayer):
     def signature(self, batch):
         from .tasks import _get
         cfg, enc_cfg = self.cfg, self._encoder_config()
-        entries = tuple(sorted((k, _describe(v)) for k, v in batch.items() if k != "n_examples_list"))
+        entries = tuple(sorted((k, self._describe_entry(v)) for k, v in batch.items() if k != "n_examples_list"))
         return (entries, tuple(batch["n_examples_list"]), _get(cfg, "train_n_clips", 1), _get(cfg, "num_frm"), _get(cfg, "score_agg_func", "mean"),
                 _get(cfg, "task"), _get(cfg, "num_labels"), bool(self.model.training), _get(cfg, "mlm_rows", "labelled"), _get(cfg, "mlm_capacity"),
                 _get(cfg, "use_mlm", True), _get(cfg, "use_itm", True), bool(self.fold_clips),
                 getattr(enc_cfg, "pixel_sampling", "host") or "host", int(getattr(enc_cfg, "pixel_random_sampling_size", 0) or 0))
+
+    def _describe_entry(self, v):
+        from .data import RawFrames
+        if self.raw_frames and isinstance(v, RawFrames):
+            # what fixes the launches: neither the byte count nor any table value -- other native resolutions replay from the same graph
+            return ("RawFrames", tuple(v.table.shape[:-1]), v.max_img_size, v.hwc, v.pixfmt, v.matrix, str(v.device))
+        return _describe(v)
+
+    def _why_eager_raw(self, rf):
+        """a RawFrames batch under raw_frames=True: why it cannot be replayed, or None"""
+        if rf.source is not None:
+            return "RawFrames batch that is indirect already (its descriptor is the caller's to point)"
+        if rf.host_table is None:
+            return "RawFrames batch without a host table (its rows cannot be checked before a replay)"
+        return self._off_device({"visual_inputs.flat": rf.flat, "visual_inputs.table": rf.table})
 
     def _why_eager(self, batch):
         from .data import RawFrames
@@ -225,7 +265,11 @@ class CapturedStep(_Replayer):
         if int(_get(cfg, "gradient_accumulation_steps", 1) or 1) > 1:
             return "gradient_accumulation_steps > 1"
         if isinstance(batch.get("visual_inputs"), RawFrames):
-            return "RawFrames batch (launch geometry from its host table)"
+            if not self.raw_frames:
+                return "RawFrames batch (launch geometry from its host table)"
+            reason = self._why_eager_raw(batch["visual_inputs"])
+            if reason is not None:
+                return reason
         enc_cfg = self._encoder_config()
         if (self.model.training and int(getattr(enc_cfg, "pixel_random_sampling_size", 0) or 0) > 0
                 and (getattr(enc_cfg, "pixel_sampling", "host") or "host") != "device"):
@@ -264,6 +308,24 @@ class CapturedStep(_Replayer):
                         fold=self.fold_clips, loss_fn=self.loss_fn)
         return fns.device_step
 
+    def _static(self, others, bufs):
+        from .data import FrameSource, RawFrames
+        static, rf = dict(others, **bufs), self._raw
+        if rf is None:
+            return static, None
+        # the body sees an indirect RawFrames over the static table and ONE descriptor: both keep their addresses, step() refills them
+        source = FrameSource(self._device())
+        table = static.pop(self.RAW_TABLE).view(*rf.table.shape)
+        static["visual_inputs"] = RawFrames.indirect(source.desc, table, rf.max_img_size, rf.hwc, None, rf.pixfmt, rf.matrix)
+        return static, source
+
+    def _stage_entry(self, entry, tensors):
+        """descriptor, then the ONE staging launch, both on the stream the replay follows on; the entry holds the batch's ``flat`` from
+        here until the next batch of its signature is staged (or the entry is evicted): a replay reads it where it lies"""
+        if entry.source is not None:
+            entry.source.point_at(self._raw.flat)
+        self._stage(entry.bufs, tensors)
+
     def _replay(self, entry):
         from . import tasks
         if entry.graph is None:                         # dry: the eager step on the static buffers
@@ -276,18 +338,31 @@ class CapturedStep(_Replayer):
 
     def step(self, batch, global_step, n_epoch=0, micro_step=0):
         from . import tasks
+        from .data import RawFrames
         batch = self._pad(batch)
         reason = self._why_eager(batch)
         sig = self.signature(batch)
         self._at = (global_step, n_epoch)
         tensors = {k: v for k, v in batch.items() if torch.is_tensor(v)}
         others = {k: (list(v) if k == "n_examples_list" else v) for k, v in batch.items() if not torch.is_tensor(v)}
+        rf = batch.get("visual_inputs")
+        self._raw = rf if self.raw_frames and reason is None and isinstance(rf, RawFrames) else None
+        if self._raw is not None:
+            # every step, replays included, BEFORE anything is staged or replayed: the rows against this batch's own byte count -- what the
+            # eager step's launch would have refused is refused here, in its words (a replay calls no validating entry point)
+            table, host = rf.packed_table()
+            ops.resize_table_check(host, rf.n_frames, rf.flat.numel(), rf.max_img_size, rf.pixfmt)
+            tensors[self.RAW_TABLE] = table             # 40 bytes per frame, in the staging launch of the text tensors
+            del others["visual_inputs"]
 
         def eager():
             return tasks.train_step(self.model, self.optimizer, batch, self.cfg, global_step, sync=self.sync, n_epoch=n_epoch,
                                     micro_step=micro_step, fold_clips=self.fold_clips, loss_fn=self.loss_fn)
 
-        return self._run(sig, tensors, others, reason, eager)
+        try:
+            return self._run(sig, tensors, others, reason, eager)
+        finally:
+            self._raw = None                            # (only the staged entry keeps the batch's bytes alive)
 
 
 class CapturedForward(_Replayer):

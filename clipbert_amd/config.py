@@ -47,7 +47,8 @@ SHARED_DEFAULTS = dict(
     weight_decay=1e-3, grad_norm=2.0, warmup_ratio=0.1, transformer_lr_mul=1.0, transformer_lr_mul_prefix="", step_decay_epochs=None,
     optim="adamw", cnn_optim="adamw", cnn_learning_rate=5e-5, cnn_weight_decay=1e-3, cnn_lr_mul=1.0, cnn_lr_mul_prefix="grid_encoder",
     cnn_lr_decay="linear", cnn_step_decay_epochs=None, freeze_cnn=0, inference_batch_size=64, inference_n_clips=1,
-    e2e_weights_path=None, detectron2_weights_path=None, bert_weights_path=None, detectron2_model_cfg="", model_config=None, seed=42)
+    e2e_weights_path=None, detectron2_weights_path=None, bert_weights_path=None, detectron2_model_cfg="", model_config=None, seed=42,
+    capture_raw_frames=0)      # this project's: start_training(capture=True) replays data.RawFrames batches too (captured.CapturedStep(raw_frames=True))
 TASK_DEFAULTS = {
     "pretraining": dict(pixel_random_sampling_size=0, pixel_sampling="host", use_itm=1, use_mlm=1),
     "video_retrieval": dict(itm_neg_size=1, classifier="mlp", cls_hidden_scale=2, margin=0.2, loss_type="ce"),

@@ -58,27 +58,48 @@ class RawFrames:
     ``pixfmt``: "rgb" (the above) or "i420" / "nv12" -- every frame is then its tightly packed YUV 4:2:0 planes (Y h x w, then U and V
     of ceil(h / 2) x ceil(w / 2) each, or the two interleaved; ``hwc`` is ignored) and ``matrix`` ("bt601": limited range, what
     libswscale applies to an untagged stream; "bt601-full", "bt709", "bt709-full") is the conversion it stands for: the RGB frames
-    tests/yuv_restatement.py spells out, nearest chroma, rounded to uint8 before the resize."""
+    tests/yuv_restatement.py spells out, nearest chroma, rounded to uint8 before the resize.
+
+    ``source``: None, or the descriptor of the indirect form (``RawFrames.indirect``: ``flat`` is then None)."""
     PIXFMTS = ("rgb", "i420", "nv12")
     MATRICES = ("bt601", "bt601-full", "bt709", "bt709-full")
 
-    def __init__(self, flat: torch.Tensor, table: torch.Tensor, max_img_size: int, hwc: bool = True,
-                 host_table: Optional[torch.Tensor] = None, pixfmt: str = "rgb", matrix: str = "bt601"):
-        assert flat.dtype == torch.uint8 and flat.dim() == 1
+    def __init__(self, flat: Optional[torch.Tensor], table: torch.Tensor, max_img_size: int, hwc: bool = True,
+                 host_table: Optional[torch.Tensor] = None, pixfmt: str = "rgb", matrix: str = "bt601", source: Optional[torch.Tensor] = None):
+        if source is None:
+            assert flat is not None and flat.dtype == torch.uint8 and flat.dim() == 1
+        else:                                   # the indirect form (RawFrames.indirect)
+            assert flat is None and tuple(source.shape) == ((16,) if source.dtype == torch.uint8 else (2,)) and \
+                source.dtype in (torch.uint8, torch.int64) and source.is_contiguous() and source.device == table.device, "source: uint8 (16,) or int64 (2,) beside the table"
         assert table.dtype == torch.int64 and table.dim() >= 1 and table.shape[-1] == 5
-        if host_table is None and not table.is_cuda:
+        if host_table is None and not table.is_cuda and source is None:
             host_table = table
         assert host_table is None or (not host_table.is_cuda and host_table.shape == table.shape)
-        self.flat, self.table, self.host_table = flat, table, host_table
+        self.flat, self.table, self.host_table, self.source = flat, table, host_table, source
         assert pixfmt in self.PIXFMTS and matrix in self.MATRICES, (pixfmt, matrix)
         self.max_img_size, self.hwc = int(max_img_size), bool(hwc)
         self.pixfmt, self.matrix = pixfmt, matrix
+
+    @classmethod
+    def indirect(cls, source: torch.Tensor, table: torch.Tensor, max_img_size: int, hwc: bool = True,
+                 host_table: Optional[torch.Tensor] = None, pixfmt: str = "rgb", matrix: str = "bt601") -> "RawFrames":
+        """The INDIRECT form: the pixels are named by a descriptor in device memory instead of ``flat`` (which is None) -- ``source``,
+        uint8 (16,) or int64 (2,) on the table's device: a cb_frame_source {base address, byte count}, which the kernel reads at run
+        time (cb_resize_pack_u8_src / cb_resize_pack_yuv420_src).  Whoever owns the descriptor re-points it between launches
+        (``FrameSource``) and keeps the bytes alive; a descriptor of 0 bytes, and every row that leaves its byte count, is an
+        all-padding frame.  It is what a captured step sees in place of the batch (captured.CapturedStep(raw_frames=True)): table and
+        descriptor keep their addresses, their contents change per step.  Everything that acts on the table rows works as on the
+        direct form; ``to`` raises (the address in the descriptor means nothing elsewhere).  No host table unless one is given: the
+        launch validates none."""
+        return cls(None, table, max_img_size, hwc, host_table, pixfmt, matrix, source=source)
 
     def _with(self, flat, table, host_table):
         """the same kind of frames (size, layout, pixel format, matrix) over other tensors"""
         return RawFrames(flat, table, self.max_img_size, self.hwc, host_table, self.pixfmt, self.matrix)
 
     def _like(self, table, host_table):
+        if self.source is not None:
+            return RawFrames.indirect(self.source, table, self.max_img_size, self.hwc, host_table, self.pixfmt, self.matrix)
         return self._with(self.flat, table, host_table)
 
     def _both(self, fn):
@@ -95,7 +116,7 @@ class RawFrames:
 
     @property
     def device(self):
-        return self.flat.device
+        return self.table.device if self.flat is None else self.flat.device
 
     dtype = torch.uint8
 
@@ -147,6 +168,8 @@ class RawFrames:
         return self if self.is_contiguous() else self._both(lambda t: t.contiguous())
 
     def to(self, device, non_blocking: bool = False):
+        if self.source is not None:
+            raise RuntimeError("RawFrames.to(): an indirect RawFrames names its bytes by a device address and cannot travel; move the direct one")
         device = torch.device(device)
         host = self.host_table if self.host_table is not None else (self.table if not self.table.is_cuda else None)
         return self._with(self.flat.to(device, non_blocking=non_blocking), self.table.to(device, non_blocking=non_blocking), host)
@@ -160,7 +183,48 @@ class RawFrames:
 
     def __repr__(self):
         kind = f"hwc={self.hwc}" if self.pixfmt == "rgb" else f"pixfmt={self.pixfmt}, matrix={self.matrix}"
-        return f"RawFrames(shape={tuple(self.shape)}, bytes={self.flat.numel()}, {kind}, device={self.device})"
+        where = "indirect" if self.flat is None else f"bytes={self.flat.numel()}"
+        return f"RawFrames(shape={tuple(self.shape)}, {where}, {kind}, device={self.device})"
+
+
+class FrameSource:
+    """The descriptor of an indirect RawFrames and its owner: ``desc``, int64 (2,) [base address, byte count] on ``device`` (a
+    cb_frame_source; 0 bytes until first pointed at something), and ``point_at(flat)``, which re-points it on the current stream and
+    holds ``flat`` until the next call.  On a GPU the two words travel through a pinned two-slot buffer, a slot being rewritten only
+    after the event behind its last upload has completed -- FusedAdamW.prepare_step's scheme; like it, never inside a capture."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.desc = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self.flat = None                               # what the descriptor names: kept alive here
+        self._cuda = self.device.type == "cuda"
+        self._host = torch.zeros(2, 2, dtype=torch.int64).pin_memory() if self._cuda else None
+        self._events = [None, None]
+        self._n = 0
+
+    def point_at(self, flat: Optional[torch.Tensor]):
+        """desc = {flat.data_ptr(), flat.numel()} ({0, 0} for None), ordered on the current stream of the device"""
+        if flat is not None:
+            assert flat.dtype == torch.uint8 and flat.dim() == 1 and flat.is_contiguous() and flat.device == self.device, "a flat uint8 buffer on the descriptor's device"
+        words = (flat.data_ptr(), flat.numel()) if flat is not None and flat.numel() else (0, 0)
+        if not self._cuda:
+            self.desc[0], self.desc[1] = words
+        else:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FrameSource.point_at() inside a hipGraph capture: a graph would freeze the address it is meant to replace")
+            slot = self._n & 1
+            self._n += 1
+            ev = self._events[slot]
+            if ev is not None:
+                ev.synchronize()                       # the copy that last read this slot has executed
+            host = self._host[slot]
+            host[0], host[1] = words
+            with torch.cuda.device(self.device):
+                self.desc.copy_(host, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+            self._events[slot] = ev
+        self.flat = flat
 
 
 def _frame_rows(rows, off: int, t: int, h: int, w: int, frame_bytes: int, max_img_size: int) -> int:
@@ -294,7 +358,11 @@ class PrefetchLoader:
 
     ``img_normalize``: ignored as a callable -- pass the model's pixel statistics at model construction instead (frames are
     delivered as uint8 and normalised inside the stem pack).  (task, batch) tuples of the reference's MetaLoader pass
-    through unchanged.  A ``RawFrames`` anywhere in a batch travels as its two tensors (flat bytes, table) through the same slots."""
+    through unchanged.  A ``RawFrames`` anywhere in a batch travels as its two tensors (flat bytes, table) through the same slots.
+
+    A batch is handed out only AFTER the consumer's current stream has been made to wait for the event behind its copies (``__iter__``:
+    wait_event, record_stream, then yield), so whatever the consumer enqueues on that stream may read the batch where it lies -- a
+    captured step's replay reads ``RawFrames.flat`` in place (captured.CapturedStep(raw_frames=True)) and needs nothing more from here."""
 
     def __init__(self, loader: Iterable, device=None, img_normalize=None, slots: int = 2):
         self.loader = loader
@@ -329,6 +397,8 @@ class PrefetchLoader:
 
     def _move(self, obj, slot, prefix=""):
         if isinstance(obj, RawFrames):                  # flat bytes and table: two keys of the pinned double buffer
+            if obj.source is not None:
+                return obj.to(self.device)                  # (raises: an indirect one cannot travel)
             table = obj.table.contiguous()
             host = obj.host_table if obj.host_table is not None else (table if not table.is_cuda else None)
             return obj._with(self._move(obj.flat, slot, f"{prefix}/flat"), self._move(table, slot, f"{prefix}/table"),
@@ -365,7 +435,7 @@ class PrefetchLoader:
     def _record_stream(obj, stream):
         if isinstance(obj, RawFrames):
             for t in (obj.flat, obj.table):
-                if t.is_cuda:
+                if t is not None and t.is_cuda:
                     t.record_stream(stream)
         elif torch.is_tensor(obj):
             if obj.is_cuda:

@@ -231,12 +231,13 @@ def _stem_forward(bb: "GridFeatBackbone", x5):
     if isinstance(x5, RawFrames):
         # ImageResize + ImagePad + ImageNorm + BGR flip of the whole ragged batch in one launch, straight into the stem's packed image
         table, host_table = x5.packed_table()
+        # (an indirect one -- the static input of a captured step -- names its bytes by a descriptor the kernel reads: the _src entry points)
+        where = dict(host_table=host_table) if x5.source is None else dict(source=x5.source)
         if x5.pixfmt == "rgb":
-            packed = ops.resize_pack_u8(x5.flat, table, n, h, rt.dtype, bb.pixel_mean, bb.pixel_std, hwc=x5.hwc, pad=3, extra_w=2,
-                                        host_table=host_table)
+            packed = ops.resize_pack_u8(x5.flat, table, n, h, rt.dtype, bb.pixel_mean, bb.pixel_std, hwc=x5.hwc, pad=3, extra_w=2, **where)
         else:                                           # the decoder's YUV 4:2:0 planes: the colour conversion rides in the same launch
             packed = ops.resize_pack_yuv420(x5.flat, table, n, h, rt.dtype, bb.pixel_mean, bb.pixel_std, layout=x5.pixfmt, matrix=x5.matrix,
-                                            pad=3, extra_w=2, host_table=host_table)
+                                            pad=3, extra_w=2, **where)
     else:
         x4 = x5.reshape(n, c, h, w)
         if not x4.is_contiguous():

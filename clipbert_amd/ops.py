@@ -232,41 +232,72 @@ def stem_pack(src: torch.Tensor, dtype: torch.dtype, pad: int = 3, mean=None, st
     return dst
 
 
-def resize_pack_u8(flat_u8: torch.Tensor, table: torch.Tensor, n: int, size: int, dtype: torch.dtype, mean, std, hwc: bool = True,
-                   pad: int = 3, extra_w: int = 0, host_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _resize_pack_args(flat_u8, table, n, host_table, source):
+    """what the two ingest wrappers ask of their tensors -> the device the image is written on"""
+    assert table.dtype == torch.int64 and tuple(table.shape) == (n, 5) and table.is_contiguous()
+    if source is not None:
+        assert flat_u8 is None and host_table is None, "source=: the bytes are named by the descriptor, and the launch validates no host table (resize_table_check)"
+        assert source.dtype in (torch.uint8, torch.int64) and source.numel() * source.element_size() == 16 and source.is_contiguous()
+        assert source.device == table.device and source.data_ptr() % 16 == 0
+        return table.device
+    assert flat_u8.dtype == torch.uint8 and flat_u8.dim() == 1 and flat_u8.is_contiguous() and table.device == flat_u8.device
+    if host_table is not None:
+        assert host_table.dtype == torch.int64 and tuple(host_table.shape) == (n, 5) and host_table.is_contiguous() and not host_table.is_cuda
+    return flat_u8.device
+
+
+def resize_pack_u8(flat_u8: Optional[torch.Tensor], table: torch.Tensor, n: int, size: int, dtype: torch.dtype, mean, std, hwc: bool = True,
+                   pad: int = 3, extra_w: int = 0, host_table: Optional[torch.Tensor] = None, source: Optional[torch.Tensor] = None) -> torch.Tensor:
     """cb_resize_pack_u8: ``n`` native-resolution uint8 RGB frames lying back to back in ``flat_u8`` -> the reference's bilinear
     resize (longer side -> ``size``) + zero pad to size x size + ImageNorm, as stem_pack's (n, size+2*pad, size+2*pad+extra_w, 4)
     BGR0 image.  ``table``: int64 (n, 5) rows [byte_offset, h, w, new_h, new_w] on flat_u8's device (clipbert_amd.data.RawFrames
-    builds it); ``host_table``: a CPU copy whose rows the library validates before the launch.  One launch, no host sync."""
-    assert flat_u8.dtype == torch.uint8 and flat_u8.dim() == 1 and flat_u8.is_contiguous()
-    assert table.dtype == torch.int64 and tuple(table.shape) == (n, 5) and table.is_contiguous() and table.device == flat_u8.device
-    if host_table is not None:
-        assert host_table.dtype == torch.int64 and tuple(host_table.shape) == (n, 5) and host_table.is_contiguous() and not host_table.is_cuda
+    builds it); ``host_table``: a CPU copy whose rows the library validates before the launch.  One launch, no host sync.
+
+    ``source`` (with ``flat_u8`` None): cb_resize_pack_u8_src -- a cb_frame_source descriptor on the table's device, uint8 (16,) or
+    int64 (2,) [base address, byte count], read by the kernel at run time: the launch depends on no address or size of the batch, so
+    a captured one serves every batch.  Bit-equal to the direct call on the same bytes; no host table is validated."""
+    dev = _resize_pack_args(flat_u8, table, n, host_table, source)
     hp, wp = size + 2 * pad, size + 2 * pad + extra_w
-    dst = torch.empty(n, hp, wp, 4, dtype=dtype, device=flat_u8.device)
+    dst = torch.empty(n, hp, wp, 4, dtype=dtype, device=dev)
+    if source is not None:
+        _chk(_lib.get().cb_resize_pack_u8_src(dtype_code(dtype), _ptr(source), _ptr(table), n, int(hwc), _f3(mean), _f3(std), _ptr(dst), size, hp,
+                                              wp, pad, _stream(table)), "cb_resize_pack_u8_src")
+        return dst
     _chk(_lib.get().cb_resize_pack_u8(dtype_code(dtype), _ptr(flat_u8), flat_u8.numel(), _ptr(table),
                                       host_table.data_ptr() if host_table is not None else None, n, int(hwc), _f3(mean), _f3(std),
                                       _ptr(dst), size, hp, wp, pad, _stream(flat_u8)), "cb_resize_pack_u8")
     return dst
 
 
-def resize_pack_yuv420(flat_u8: torch.Tensor, table: torch.Tensor, n: int, size: int, dtype: torch.dtype, mean, std, layout: str = "i420",
-                       matrix: str = "bt601", pad: int = 3, extra_w: int = 0, host_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+def resize_pack_yuv420(flat_u8: Optional[torch.Tensor], table: torch.Tensor, n: int, size: int, dtype: torch.dtype, mean, std, layout: str = "i420",
+                       matrix: str = "bt601", pad: int = 3, extra_w: int = 0, host_table: Optional[torch.Tensor] = None,
+                       source: Optional[torch.Tensor] = None) -> torch.Tensor:
     """cb_resize_pack_yuv420: resize_pack_u8 for ``n`` YUV 4:2:0 frames lying back to back in ``flat_u8`` as their tightly packed
     planes -- ``layout`` "i420" (Y, U, V) or "nv12" (Y, interleaved UV), h * w + 2 * ceil(h / 2) * ceil(w / 2) bytes each -- converted
     with ``matrix`` ("bt601", "bt601-full", "bt709", "bt709-full"; nearest chroma) tap by tap.  Bit-equal to resize_pack_u8(hwc=False)
-    on the converted uint8 RGB frames.  ``table`` / ``host_table`` as there.  One launch, no host sync."""
-    assert flat_u8.dtype == torch.uint8 and flat_u8.dim() == 1 and flat_u8.is_contiguous()
-    assert table.dtype == torch.int64 and tuple(table.shape) == (n, 5) and table.is_contiguous() and table.device == flat_u8.device
-    if host_table is not None:
-        assert host_table.dtype == torch.int64 and tuple(host_table.shape) == (n, 5) and host_table.is_contiguous() and not host_table.is_cuda
+    on the converted uint8 RGB frames.  ``table`` / ``host_table`` / ``source`` (cb_resize_pack_yuv420_src) as there.  One launch, no
+    host sync."""
+    dev = _resize_pack_args(flat_u8, table, n, host_table, source)
     hp, wp = size + 2 * pad, size + 2 * pad + extra_w
-    dst = torch.empty(n, hp, wp, 4, dtype=dtype, device=flat_u8.device)
+    dst = torch.empty(n, hp, wp, 4, dtype=dtype, device=dev)
+    if source is not None:
+        _chk(_lib.get().cb_resize_pack_yuv420_src(dtype_code(dtype), _ptr(source), _ptr(table), n, _lib.YUV_LAYOUTS[layout], _lib.YUV_MATRICES[matrix],
+                                                  _f3(mean), _f3(std), _ptr(dst), size, hp, wp, pad, _stream(table)), "cb_resize_pack_yuv420_src")
+        return dst
     _chk(_lib.get().cb_resize_pack_yuv420(dtype_code(dtype), _ptr(flat_u8), flat_u8.numel(), _ptr(table),
                                           host_table.data_ptr() if host_table is not None else None, n, _lib.YUV_LAYOUTS[layout],
                                           _lib.YUV_MATRICES[matrix], _f3(mean), _f3(std), _ptr(dst), size, hp, wp, pad, _stream(flat_u8)),
          "cb_resize_pack_yuv420")
     return dst
+
+
+def resize_table_check(host_table: torch.Tensor, n: int, flat_bytes: int, size: int, pixfmt: str = "rgb") -> None:
+    """cb_resize_table_check: the row rules of the two direct entry points on a HOST table against a buffer of ``flat_bytes`` bytes, no
+    launch -- what a replayed step runs on a batch before it stages it.  Raises the RuntimeError the direct launch would have raised
+    (the same text, the direct entry point's name included)."""
+    assert host_table.dtype == torch.int64 and tuple(host_table.shape) == (n, 5) and host_table.is_contiguous() and not host_table.is_cuda
+    _chk(_lib.get().cb_resize_table_check(host_table.data_ptr(), n, int(flat_bytes), size, _lib.PIXFMTS[pixfmt]),
+         "cb_resize_pack_u8" if pixfmt == "rgb" else "cb_resize_pack_yuv420")
 
 
 def image_norm(frames_u8: torch.Tensor, mean, std) -> torch.Tensor:

@@ -387,7 +387,9 @@ def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=N
     ``capture``: False (default) = every step is the eager train_step.  True = the steps go through clipbert_amd.captured.CapturedStep:
     a batch signature seen twice is captured as a hipGraph and replayed from then on, everything a graph must not freeze falls back to
     train_step with a warning (see that module).  "dry" = its bookkeeping without graphs (tests), or pass a CapturedStep built by the
-    caller (``max_graphs``, ``pad_text_to``) on the SAME model, optimizer, loss_fn, fold_clips and sync (checked)."""
+    caller (``max_graphs``, ``pad_text_to``, ``raw_frames``) on the SAME model, optimizer, loss_fn, fold_clips and sync (checked); it is
+    used as it is.  cfg.capture_raw_frames = 1 (default 0) builds the stepper with ``raw_frames=True``: data.RawFrames batches replay as
+    well, read where the loader put them (their bytes are never staged; the stepper keeps the batch's buffer alive until the next one)."""
     from .data import InfiniteIterator
     stepper = None
     if capture:
@@ -400,7 +402,8 @@ def start_training(model, optimizer, train_loader, cfg, sync=None, validate_fn=N
             if differ:                                      # (e.g. an object without the loop's multi-rank sync would capture a step without the exchange)
                 raise ValueError(f"start_training(capture=CapturedStep): the object was built with another {' / '.join(differ)} than the loop was called with")
         else:
-            stepper = CapturedStep(model, optimizer, cfg, loss_fn=loss_fn, fold_clips=fold_clips, sync=sync, mode="dry" if capture == "dry" else "graph")
+            stepper = CapturedStep(model, optimizer, cfg, loss_fn=loss_fn, fold_clips=fold_clips, sync=sync, mode="dry" if capture == "dry" else "graph",
+                                   raw_frames=bool(_get(cfg, "capture_raw_frames", 0)))
     if sync is not None and sync.world > 1 and overlap and model.rt is not None and model.rt.after_encoder_backward is None:
         sync.attach(model)
     acc = max(1, int(_get(cfg, "gradient_accumulation_steps", 1) or 1))

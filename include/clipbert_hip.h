@@ -264,6 +264,33 @@ int cb_resize_pack_yuv420(int32_t dtype, const uint8_t* flat, int64_t flat_bytes
                           int32_t layout, int32_t matrix, const float* mean3, const float* std3, void* dst, int32_t S, int32_t Hp, int32_t Wp,
                           int32_t pad, void* stream);
 
+/* The same two launches with the source buffer named by a DESCRIPTOR IN DEVICE MEMORY instead of by kernel arguments: a captured
+ * launch (hipGraph) freezes its arguments, and a training loop's batches arrive in a new buffer of another size every step (the
+ * reference's PrefetchLoader, src/datasets/dataloader.py:86-152: fresh .cuda(non_blocking=True) tensors per batch).  With these entry
+ * points the launch depends on (N, S, Hp, Wp, pad) only: the caller rewrites the 16 bytes of *src and the table rows between replays
+ * (stream-ordered with them) and the batch is read where the loader put it -- no staging copy of the pixel bytes.
+ *   src : DEVICE, 16-byte aligned.  The kernel reads base and bytes from it (one address for the whole grid) and then runs the very
+ *         pixel routine of the direct entry points: for the same bytes, table and parameters the output is bit-equal to theirs.
+ *         bytes = 0 -- the state a freshly allocated descriptor must be given -- makes every frame all padding and reads nothing
+ *         through base; so does every row that leaves [0, bytes).
+ * Every other argument means what it means in cb_resize_pack_u8 / cb_resize_pack_yuv420.  Nothing is validated on the host but these
+ * arguments themselves (null pointers, alignment, N, S, pad, Hp, Wp): there is no table_host here -- a caller that wants the direct
+ * entry points' refusal of a bad row runs cb_resize_table_check on its host table first. */
+typedef struct __attribute__((aligned(16))) cb_frame_source {
+    const uint8_t* base; /* the buffer the table's byte offsets count from */
+    int64_t bytes;       /* its size: no byte at or past base + bytes is read */
+} cb_frame_source;
+int cb_resize_pack_u8_src(int32_t dtype, const cb_frame_source* src, const int64_t* table, int32_t N, int32_t hwc, const float* mean3,
+                          const float* std3, void* dst, int32_t S, int32_t Hp, int32_t Wp, int32_t pad, void* stream);
+int cb_resize_pack_yuv420_src(int32_t dtype, const cb_frame_source* src, const int64_t* table, int32_t N, int32_t layout, int32_t matrix,
+                              const float* mean3, const float* std3, void* dst, int32_t S, int32_t Hp, int32_t Wp, int32_t pad, void* stream);
+/* HOST ONLY, no launch: the row rules that cb_resize_pack_u8 (pixfmt = CB_PIXFMT_RGB) / cb_resize_pack_yuv420 (CB_PIXFMT_I420,
+ * CB_PIXFMT_NV12: the same byte count) apply to their table_host, on N rows against a buffer of flat_bytes bytes at size S -- sizes
+ * in 1..16384, new sizes in 1..S, offset >= 0 and the frame's bytes inside the buffer.  0 = every row describes a frame inside the
+ * buffer; -1 with the message (cb_last_error) the direct entry point gives, its name included: they call this function. */
+enum { CB_PIXFMT_RGB = 0, CB_PIXFMT_I420 = 1, CB_PIXFMT_NV12 = 2 };
+int cb_resize_table_check(const int64_t* table_host, int32_t N, int64_t flat_bytes, int32_t S, int32_t pixfmt);
+
 /* ImageNorm alone (a1): uint8 (n) -> fp32 (x - mean[c]) / std[c], NCHW with plane size hw.
  * mean3 / std3: HOST arrays of 3 floats. */
 int cb_image_norm(const uint8_t* src, float* dst, const float* mean3, const float* std3,
@@ -594,7 +621,9 @@ const char* cb_last_error(void);
  * 14 = cb_gemm_desc grew by res_rowmap / res_rows / dgrad_s2 at its END (zero = off: the residual through a row map of its own and the
  *      3x3 stride-2 data gradient by parity classes -- the "tail form" of a bottleneck block whose consumer reads even pixels only);
  * 15 = cb_pixel_sample (the pre-training pixel sub-sampling drawn on the device; nothing else changed);
- * 16 = cb_mc_predict (the MSRVTT multiple-choice scoring: pooling, probability and arg-max per question; nothing else changed) */
+ * 16 = cb_mc_predict (the MSRVTT multiple-choice scoring: pooling, probability and arg-max per question; nothing else changed);
+ * 17 = cb_frame_source, cb_resize_pack_u8_src, cb_resize_pack_yuv420_src, cb_resize_table_check (the raw-frame ingest from a buffer
+ *      named in device memory, for captured steps; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
