@@ -1,31 +1,14 @@
 // MSRVTT multiple-choice scoring (src/tasks/run_msrvtt_mc.py:172-195): the clip pooling, the row's probability and the arg-max over each
 // question's options in ONE launch over the fp32 stack of per-clip logits -- in place of the pooling, logsumexp, softmax and max launches
 // and the per-clip device-to-host copies of the runner.
-#include "common.h"
+#include "clip_pool.h"
 
 namespace {
 
 constexpr int kMcThreads = 256;
 constexpr int kMcWaves = kMcThreads / 64;
-constexpr int kMcNone = 0x7fffffff;                           // "no option seen yet": every real index beats it
 
 __device__ __forceinline__ bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
-// pooled logit of one class over the clips; x[k * stride] is clip k.  The arithmetic of clip_agg_fwd_kernel (misc.hip).
-__device__ __forceinline__ void pool_begin(float v, float& m, float& s) { m = v; s = v; }
-__device__ __forceinline__ void pool_add(float v, float& m, float& s) {
-    m = v > m || v != v ? v : m;                              // (a NaN stays a NaN: torch.max propagates it)
-    s += v;
-}
-
-// does (bm, bi) replace (am, ai)?  The larger score; among equals the lower index; a NaN is larger than any number (torch.max).
-__device__ __forceinline__ bool mc_better(float am, int ai, float bm, int bi) {
-    if (bi == kMcNone) return false;
-    if (ai == kMcNone) return true;
-    const bool an = am != am, bn = bm != bm;
-    if (an || bn) return bn && (!an || bi < ai);
-    return bm > am || (bm == am && bi < ai);
-}
 
 // sigmoid(d) without an overflowing exponential: z = exp(-|d|) <= 1
 __device__ __forceinline__ float mc_sigmoid(float d) {
@@ -57,14 +40,7 @@ __device__ __forceinline__ float mc_row_score(const float* x, int64_t clip_strid
     float pooled[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) {
-        if (mode == CB_AGG_MEAN) pooled[c] = s[c] / (float)n_clips;
-        else if (mode == CB_AGG_MAX) pooled[c] = m[c];
-        else if (!(fabsf(m[c]) <= 3.0e38f)) pooled[c] = m[c];   // an infinite or NaN maximum is the result (torch.logsumexp)
-        else {                                                // log-sum-exp over the clips, shifted by their maximum (a second pass: a few KB, L1-resident)
-            float e = 0.f;
-            for (int k = 0; k < n_clips; ++k) e += expf(x[(int64_t)k * clip_stride + c] - m[c]);
-            pooled[c] = m[c] + logf(e);
-        }
+        pooled[c] = pool_finish(m[c], s[c], x + c, clip_stride, n_clips, mode);                      // (clip_pool.h: shared with qa.hip)
     }
     return mc_sigmoid(C == 2 ? pooled[C - 1] - pooled[0] : pooled[0]);
 }
@@ -88,15 +64,7 @@ __global__ void __launch_bounds__(kMcThreads) mc_predict_kernel(const float* log
             bi = o;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float om = __shfl_xor(bm, off);
-        const int oi = __shfl_xor(bi, off);
-        if (mc_better(bm, bi, om, oi)) {
-            bm = om;
-            bi = oi;
-        }
-    }
+    wave_best(bm, bi);
     if (lane == 0) pred[q] = bi;
 }
 

@@ -337,6 +337,34 @@ def collate_mc(videos, option_ids, option_mask, question_ids, answers=None) -> D
     return batch
 
 
+def collate_qa(videos, text_ids, text_mask, question_ids, labels=None, n_options: int = 1) -> Dict:
+    """The tensor half of VideoQACollator.collate_batch (src/datasets/dataset_video_qa.py:193-227) from already tokenised text -- for
+    tasks.qa_clip_logits / validate_video_qa, whose loaders hold one question per video.  ``videos``: B tensors (n_clips*num_frm, 3, H,
+    W) of one shape (or the stacked tensor); ``text_ids`` / ``text_mask``: per video the (n_options, L) rows "question + option" of the
+    multiple-choice tasks (action / transition: n_options = 5) or its one (L,) question (n_options = 1), as B tensors, stacked, or
+    already flat (B*n_options, L); ``labels``: one answer per question (the right option, the answer id, or the count) or None, as the
+    reference's default_collate of ints gives them (int64).  Returns visual_inputs, text_input_ids / text_input_mask (B*n_options, L),
+    question_ids, labels and n_examples_list [1]*B."""
+    vis = videos if torch.is_tensor(videos) else torch.stack(list(videos))
+    bsz, n_options = vis.shape[0], int(n_options)
+    question_ids = list(question_ids)
+
+    def flat(x):
+        x = x if torch.is_tensor(x) else torch.stack(list(x))
+        return x.reshape(-1, x.shape[-1])
+
+    ids, mask = flat(text_ids), flat(text_mask)
+    if len(question_ids) != bsz or ids.shape != mask.shape or ids.shape[0] != bsz * n_options:
+        raise ValueError(f"collate_qa: {bsz} videos of {n_options} text rows each, {len(question_ids)} question ids, text ids "
+                         f"{tuple(ids.shape)}, mask {tuple(mask.shape)}")
+    if labels is not None:
+        labels = torch.as_tensor([int(a) for a in labels] if not torch.is_tensor(labels) else labels).reshape(-1)
+        if labels.numel() != bsz:
+            raise ValueError(f"collate_qa: {labels.numel()} labels for {bsz} questions")
+    return dict(visual_inputs=vis, text_input_ids=ids, text_input_mask=mask, question_ids=question_ids, labels=labels,
+                n_examples_list=[1] * bsz)
+
+
 class InfiniteIterator:
     """iterate an iterable object infinitely (src/datasets/dataloader.py:155-175)"""
     def __init__(self, iterable):

@@ -702,6 +702,37 @@ def mc_predict(stack: torch.Tensor, n_options: int, mode: int, clip_stride: Opti
     return scores, pred
 
 
+QA_CLASSIFY, QA_COUNT = 0, 1
+
+
+def qa_predict(stack: torch.Tensor, mode: int, kind: int = QA_CLASSIFY, labels: Optional[torch.Tensor] = None, want_pooled: bool = False,
+               clip_stride: Optional[int] = None):
+    """cb_qa_predict on the fp32 stack (n_clips, n_q, C) of per-clip logits; each clip contiguous, the dim-0 stride may exceed n_q * C (a
+    view of a padded buffer; ``clip_stride`` overrides it, in elements) -> (pred int32 (n_q,), loss fp32 (n_q,) | None, pooled fp32
+    (n_q, C) | None).  ``kind`` QA_CLASSIFY: pred = the arg-max over the classes of the logits pooled over the clips with ``mode``
+    (AGG_MEAN | AGG_MAX | AGG_LSE), ``labels`` int32 (n_q,) class ids, loss = the mean over the clips of the per-clip cross entropy;
+    QA_COUNT (C == 1): pred = clamp(trunc(pooled + 0.5), 1, 10), ``labels`` fp32 (n_q,), loss = the mean over the clips of the squared
+    error.  Without ``labels`` there is no loss.  One launch, no host synchronisation."""
+    if stack.dim() != 3 or stack.dtype != torch.float32:
+        raise ValueError(f"qa_predict: expected an fp32 (n_clips, n_q, C) stack, got {stack.dtype} {tuple(stack.shape)}")
+    n_clips, n_q, c = stack.shape
+    if n_q * c > 1 and not stack[0].is_contiguous():
+        raise ValueError("qa_predict: each clip's (n_q, C) logits must be contiguous")
+    if labels is not None:
+        want = torch.float32 if int(kind) == QA_COUNT else torch.int32
+        if labels.dtype != want or labels.numel() != n_q or not labels.is_contiguous() or labels.device != stack.device:
+            raise ValueError(f"qa_predict: labels must be {n_q} contiguous {want} values on {stack.device}, got {labels.dtype} "
+                             f"{tuple(labels.shape)} on {labels.device}")
+    if clip_stride is None:
+        clip_stride = stack.stride(0) if n_clips > 1 else max(stack.stride(0), n_q * c)
+    pred = torch.empty(n_q, dtype=torch.int32, device=stack.device)
+    loss = torch.empty(n_q, dtype=torch.float32, device=stack.device) if labels is not None else None
+    pooled = torch.empty(n_q, c, dtype=torch.float32, device=stack.device) if want_pooled else None
+    _chk(_lib.get().cb_qa_predict(_ptr(stack), int(clip_stride), n_clips, n_q, c, int(mode), int(kind), _ptr(labels), _ptr(pred), _ptr(loss),
+                                  _ptr(pooled), _stream(stack)), "cb_qa_predict")
+    return pred, loss, pooled
+
+
 def colsum(g, out, m=None, n=None, ldg=None):
     """out[n] += sum_m g[m, n] (fp32 atomics)."""
     m = g.shape[0] if m is None else m

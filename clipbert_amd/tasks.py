@@ -755,6 +755,170 @@ def validate_qa(model, val_loader, cfg, group=None, fold_clips: bool = True):
     return rows, log
 
 
+# ---- video QA validation on the device (run_video_qa.py:216-362, dataset_video_qa.py:131-183) ------------------------------------------
+QA_MC_TASKS = ("action", "transition")                     # one text row per (question, option) pair
+QA_CLASSIFY_TASKS = QA_MC_TASKS + ("frameqa", "msrvtt_qa")  # arg-max answers; everything else ("count") is the clamped regression
+QA_ANSWER_TYPES = dict(frameqa=("object", "number", "color", "location"),          # answer_type2idx of evaluate_tgif_qa (:147-150)
+                       msrvtt_qa=("what", "who", "how", "where", "when"))
+
+
+@torch.no_grad()
+def qa_clip_logits(model, batch: Dict, cfg, cache_cnn: bool = True, max_pairs_per_pass: int = 256, capture=None) -> torch.Tensor:
+    """The clip loop of the QA validation (:245-261) -> the fp32 (inference_n_clips, B, C) stack of per-clip logits, on the device.  ``batch``
+    has the keys of VideoQACollator (data.collate_qa) with ONE question per video, as the validation loaders are built (:98); anything
+    else raises ValueError.  action / transition: cfg.num_labels text rows per video, C = cfg.num_labels (the head's view(-1, num_labels));
+    frameqa / msrvtt_qa / count: one text row per video, C = the head's width.  This is mc_clip_logits -- the same CNN batch, encoder passes
+    of at most ``max_pairs_per_pass`` pairs over clip-major (clip, video) blocks and ``capture`` choices; cache_cnn=False is the
+    reference's order, one full forward per clip with forward_step's multiplied counts (:206-210) -- with the task's rows per video.  The
+    batch's labels are not passed into the model."""
+    n_options = int(_get(cfg, "num_labels")) if _get(cfg, "task", "action") in QA_MC_TASKS else 1
+    stack = mc_clip_logits(model, batch, cfg, n_options=n_options, cache_cnn=cache_cnn, max_pairs_per_pass=max_pairs_per_pass, capture=capture)
+    return stack.reshape(stack.shape[0], len(batch["n_examples_list"]), -1)
+
+
+@torch.no_grad()
+def qa_predict_batch(model, batch: Dict, cfg, cache_cnn: bool = True, max_pairs_per_pass: int = 256, capture=None):
+    """(pred int32 (B,), loss fp32 (B,) | None) of one batch, both on the device: qa_clip_logits, then the pooling over the clips
+    (cfg.score_agg_func), the answer (:273-279) and -- with batch["labels"] -- each question's loss, the mean over the clips of its
+    per-clip cross entropy / squared error (what :250-259 sums), in one launch (ops.qa_predict).  No host synchronisation."""
+    mode = _agg_mode(_get(cfg, "score_agg_func", "mean"))
+    count = _get(cfg, "task", "action") not in QA_CLASSIFY_TASKS
+    stack = qa_clip_logits(model, batch, cfg, cache_cnn=cache_cnn, max_pairs_per_pass=max_pairs_per_pass, capture=capture)
+    labels = batch.get("labels")
+    if labels is not None:
+        labels = torch.as_tensor(labels).reshape(-1).to(device=stack.device, dtype=torch.float32 if count else torch.int32).contiguous()
+    pred, loss, _pooled = ops.qa_predict(stack, mode, kind=ops.QA_COUNT if count else ops.QA_CLASSIFY, labels=labels)
+    return pred, loss
+
+
+def video_qa_counters(pred, gt, answer_types: Optional[Sequence[str]], task: str, loss_sum: float = 0.0) -> Dict:
+    """The additive counters of one rank: n, hits, abs_err (the sum of |pred - gt|: the count task's error), loss_sum and, for frameqa /
+    msrvtt_qa with ``answer_types`` (one of QA_ANSWER_TYPES[task] per question), type_n / type_hits per type.  ``pred`` / ``gt``: integer
+    arrays (answer ids, options or counts; a ground truth outside the vocabulary is any id no prediction takes, e.g. -1)."""
+    p, g = np.asarray(pred, dtype=np.int64).reshape(-1), np.asarray(gt, dtype=np.int64).reshape(-1)
+    assert p.shape == g.shape, (p.shape, g.shape)
+    hit = p == g
+    c = dict(n=int(p.size), hits=int(hit.sum()), abs_err=int(np.abs(p - g).sum()), loss_sum=float(loss_sum))
+    if task in QA_ANSWER_TYPES and answer_types is not None:
+        types = np.asarray(list(answer_types))
+        assert types.shape == p.shape, (types.shape, p.shape)
+        unknown = set(types.tolist()) - set(QA_ANSWER_TYPES[task])
+        if unknown:
+            raise KeyError(f"unknown answer type(s) {sorted(unknown)}: expected one of {QA_ANSWER_TYPES[task]}")
+        c["type_n"] = {t: int((types == t).sum()) for t in QA_ANSWER_TYPES[task]}
+        c["type_hits"] = {t: int(hit[types == t].sum()) for t in QA_ANSWER_TYPES[task]}
+    return c
+
+
+def merge_video_qa_counters(parts: Sequence[Dict]) -> Dict:
+    """the counters of several ranks (or batches) added up, in the order given"""
+    out = dict(n=0, hits=0, abs_err=0, loss_sum=0.0)
+    for c in parts:
+        for k in ("n", "hits", "abs_err", "loss_sum"):
+            out[k] += c[k]
+        for k in ("type_n", "type_hits"):
+            if k in c:
+                tgt = out.setdefault(k, {})
+                for t, v in c[k].items():
+                    tgt[t] = tgt.get(t, 0) + v
+    return out
+
+
+def video_qa_metrics(counters: Dict, task: str, per_rank: bool = False) -> Dict:
+    """The score dict from (merged) counters.  per_rank=True: what evaluate_tgif_qa returns for one rank (dataset_video_qa.py:167-183) --
+    overall_acc and the per-type *_acc as fractions (0 for an empty type), ratios = {type_ratio: [share, count]}.  per_rank=False: the
+    gathered scores of validate (:304-348) -- the accuracies as get_rounded_percentage (round(100 x, 2); count: round(x, 2)), ratios =
+    {type_ratio: [rounded percentage of all questions, count]} -- from exact integer sums where the reference re-weights per-rank means:
+    the same value up to rounding."""
+    n = counters["n"]
+    classify = task in QA_CLASSIFY_TASKS
+
+    def shown(x):
+        return x if per_rank else (round(x * 100, 2) if classify else round(x, 2))
+
+    scores = dict(overall_acc=shown(counters["hits"] / n if n else float("nan")))      # (np.mean of nothing is nan in the reference too)
+    if "type_n" in counters:
+        ratios = {}
+        for t, cnt in counters["type_n"].items():
+            scores[f"{t}_acc"] = shown(counters["type_hits"][t] / cnt) if cnt else 0
+            share = 1. * cnt / n
+            ratios[f"{t}_ratio"] = [share if per_rank else round(share * 100, 2), cnt]
+        scores["ratios"] = ratios
+    return scores
+
+
+def video_qa_scores(pred, gt, answer_types: Optional[Sequence[str]], task: str) -> Dict:
+    """ClipBertVideoQADataset.evaluate_tgif_qa (dataset_video_qa.py:131-183) for one rank, on integer arrays and a list of answer-type names
+    instead of the dataset's qid2data: overall_acc, and for frameqa / msrvtt_qa the per-type *_acc and ratios."""
+    return video_qa_metrics(video_qa_counters(pred, gt, answer_types, task), task, per_rank=True)
+
+
+@torch.no_grad()
+def validate_video_qa(model, val_loader, cfg, qid2data: Optional[Dict] = None, label2ans: Optional[Dict] = None, eval_score: bool = True,
+                      group=None, cache_cnn: bool = True, capture=False, val_log: Optional[Dict] = None):
+    """validate of run_video_qa.py:216-362 over the batches of THIS rank -> (qa_results, gathered_scores).  ``val_loader`` yields the
+    batches of data.collate_qa.  Per batch one qa_predict_batch; predictions, losses and labels stay on the device until the loader is
+    exhausted, then one concatenation and one transfer bring them to the host.  qa_results: dict(question_id, answer: the int the
+    reference stores, and data=qid2data[qid] when ``qid2data`` is given) per question of this rank.  gathered_scores (eval_score=True):
+    video_qa_metrics of the counters of all ranks, merged through one all_gather_object; the ground truth is qid2data[qid]["answer"] /
+    ["answer_type"] when ``qid2data`` is given (frameqa / msrvtt_qa: answer strings, mapped through ``label2ans`` {id: answer} as the
+    reference maps the predictions), else batch["labels"] and batch.get("answer_types").  eval_score=False (test sets without answers):
+    gathered_scores == 0.  ``val_log`` (a dict, optional) receives what the reference logs: valid/loss -- the summed loss over the number
+    of questions, 0 without labels -- and one valid/<k> per non-ratio score.  ``capture``: handed to every qa_clip_logits.  The model is
+    put in eval mode for the loop and returned to its mode."""
+    task = _get(cfg, "task", "action")
+    was_training = model.training
+    model.eval()
+    try:
+        qids: List = []
+        types: List = []
+        packed: List[torch.Tensor] = []
+        have_loss = have_labels = True
+        for batch in val_loader:
+            q = list(batch["question_ids"])
+            assert len(q) == len(batch["n_examples_list"]), (len(q), len(batch["n_examples_list"]))
+            pred, loss = qa_predict_batch(model, {k: v for k, v in batch.items() if k not in ("question_ids", "answer_types")}, cfg,
+                                          cache_cnn=cache_cnn, capture=capture or None)
+            labels = batch.get("labels")
+            have_loss, have_labels = have_loss and loss is not None, have_labels and labels is not None
+            zero = torch.zeros_like(pred)
+            lab = zero if labels is None else torch.as_tensor(labels).reshape(-1).to(device=pred.device, dtype=torch.int32)
+            packed.append(torch.stack([pred, zero if loss is None else loss.view(torch.int32), lab]))       # (the loss travels as its bits)
+            qids.extend(q)
+            if batch.get("answer_types") is not None:
+                types.extend(batch["answer_types"])
+        host = (packed[0] if len(packed) == 1 else torch.cat(packed, dim=1)).cpu() if packed else torch.zeros(3, 0, dtype=torch.int32)
+    finally:
+        model.train(was_training)
+    answers = host[0].tolist()
+    loss_sum = float(host[1].view(torch.float32).double().sum()) if have_loss else 0.0
+    qa_results = [dict(question_id=q, answer=a, **({} if qid2data is None else dict(data=qid2data[q]))) for q, a in zip(qids, answers)]
+    n_ex = len(qids)
+    if not eval_score:
+        total = merge_video_qa_counters(_all_gather_scalar(dict(n=n_ex, hits=0, abs_err=0, loss_sum=loss_sum), group))
+        gathered_scores = 0
+    else:
+        if qid2data is not None:
+            gt, types = [qid2data[q]["answer"] for q in qids], [qid2data[q].get("answer_type") for q in qids]
+            if task in QA_ANSWER_TYPES:                     # answer strings -> ids; an answer outside the vocabulary matches no prediction
+                if label2ans is None:
+                    raise ValueError(f"validate_video_qa: the ground truth of task {task!r} is an answer string: label2ans is needed")
+                ans2label = {v: int(k) for k, v in label2ans.items()}
+                gt = [ans2label.get(g, -1) for g in gt]
+        elif have_labels:
+            gt = host[2].tolist()
+        else:
+            raise ValueError("validate_video_qa(eval_score=True) needs the answers: qid2data, or labels in every batch")
+        use_types = types if task in QA_ANSWER_TYPES and len(types) == n_ex and n_ex else None
+        total = merge_video_qa_counters(_all_gather_scalar(video_qa_counters(answers, gt, use_types, task, loss_sum), group))
+        gathered_scores = video_qa_metrics(total, task)
+    if val_log is not None:
+        val_log["valid/loss"] = float(total["loss_sum"] / total["n"]) if total["n"] else float("nan")
+        if eval_score:
+            val_log.update({f"valid/{k}": v for k, v in gathered_scores.items() if "ratio" not in k})
+    return qa_results, gathered_scores
+
+
 # ---- metrics (:519-625) ------------------------------------------------------------------------------------------------
 def retrieval_metrics_from_scores(score_matrix, gt_cols: Sequence[int]) -> Dict[str, float]:
     """score_matrix (#queries, #candidates), gt_cols[i] = index of query i's ground-truth candidate -> recall@{1,5,10} in %,

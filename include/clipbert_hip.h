@@ -539,6 +539,18 @@ int cb_retrieval_scores(const float* logits, float* out, int64_t rows, int32_t C
  * n_q >= 1: a question's options are reduced inside one wave. */
 int cb_mc_predict(const float* logits, int64_t clip_stride, int32_t n_clips, int32_t n_q, int32_t n_options, int32_t C, int32_t mode,
                   float* scores, int32_t* pred, void* stream);
+/* Video-QA validation (src/tasks/run_video_qa.py:241-279 and the loss of :250-259) in ONE launch, no workspace, no atomics.  logits: the fp32
+ * stack, clip k, question q, class c at logits[k * clip_stride + q * C + c], clip_stride >= n_q * C (a padded stack is legal).
+ * pooled[q, c] (fp32, n_q * C, may be null) = the class's logits pooled over the clips with mode CB_AGG_MEAN | CB_AGG_MAX | CB_AGG_LSE, the
+ * arithmetic of cb_mc_predict.  kind CB_QA_CLASSIFY: pred[q] (int32) = arg-max_c pooled[q, c] -- the lowest index among equals, a NaN larger
+ * than any number (torch.max); labels: int32 (n_q) class ids; loss[q] = (1 / n_clips) sum_k (logsumexp_c x[k, q, :] - x[k, q, label]),
+ * max-shifted (a label outside [0, C) gives NaN).  kind CB_QA_COUNT (C == 1): pred[q] = clamp(trunc(pooled[q] + 0.5), 1, 10), clamped
+ * before the integer conversion (a NaN gives 1); labels: fp32 (n_q); loss[q] = (1 / n_clips) sum_k (x[k, q] - label)^2.  loss (fp32, n_q) is
+ * written only when both labels and loss are given.  C <= 64 runs one wave per question; larger C one workgroup per question, whose loss
+ * takes at most 256 clips. */
+enum { CB_QA_CLASSIFY = 0, CB_QA_COUNT = 1 };
+int cb_qa_predict(const float* logits, int64_t clip_stride, int32_t n_clips, int32_t n_q, int32_t C, int32_t mode, int32_t kind,
+                  const void* labels, int32_t* pred, float* loss, float* pooled, void* stream);
 /* Mean of n per-example losses (the runners' loss.mean(), run_video_retrieval.py:422) and its backward
  * dx[i] = *dmean / n; `*counter += inc` on a device word (the dropout seed word a captured step advances). */
 int cb_mean_fwd(const float* x, int64_t n, float* out, void* stream);
@@ -623,7 +635,8 @@ const char* cb_last_error(void);
  * 15 = cb_pixel_sample (the pre-training pixel sub-sampling drawn on the device; nothing else changed);
  * 16 = cb_mc_predict (the MSRVTT multiple-choice scoring: pooling, probability and arg-max per question; nothing else changed);
  * 17 = cb_frame_source, cb_resize_pack_u8_src, cb_resize_pack_yuv420_src, cb_resize_table_check (the raw-frame ingest from a buffer
- *      named in device memory, for captured steps; nothing else changed) */
+ *      named in device memory, for captured steps; nothing else changed);
+ * 18 = cb_qa_predict (the video-QA validation: pooling, answer and loss per question; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
