@@ -85,6 +85,7 @@ _SIGNATURES = {
     "cb_retrieval_scores": [vp, vp, i64, i32, vp],
     "cb_mc_predict": [vp, i64, i32, i32, i32, i32, i32, vp, vp, vp],
     "cb_qa_predict": [vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+    "cb_retrieval_rank": [vp, i64, i32, i32, i32, vp, vp, vp, i64, vp],
     "cb_sq_sum_fold": [vp, vp, i32, vp, i64, vp, vp, i32, vp],
     "cb_mean_fwd": [vp, i64, vp, vp],
     "cb_mean_bwd": [vp, i64, vp, vp],

@@ -670,14 +670,49 @@ def head_loss(kind: int, x, y=None, want_loss=True, dloss=None, want_grad=False,
     return loss, dx
 
 
-def retrieval_scores(logits) -> torch.Tensor:
-    """(rows, 2) -> softmax[:, 1]; (rows, 1) or (rows,) -> sigmoid; fp32"""
+def retrieval_scores(logits, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(rows, 2) -> softmax[:, 1]; (rows, 1) or (rows,) -> sigmoid; fp32.  ``out``: a contiguous fp32 (rows,) slice on the logits' device
+    to write in place (a piece of a score-matrix row); None = a fresh tensor."""
     assert logits.dtype == torch.float32 and logits.is_contiguous()
     c = logits.shape[1] if logits.dim() == 2 else 1
     rows = logits.numel() // c
-    out = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows,) or not out.is_contiguous() or out.device != logits.device:
+        raise ValueError(f"retrieval_scores: out must be {rows} contiguous fp32 values on {logits.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
     _chk(_lib.get().cb_retrieval_scores(_ptr(logits), _ptr(out), rows, c, _stream(logits)), "cb_retrieval_scores")
     return out
+
+
+RANK_ROW_QUERIES, RANK_COL_QUERIES = 0, 1          # CB_RANK_*: which axis of the video-major score matrix holds the queries
+
+
+def retrieval_rank(scores: torch.Tensor, gt: torch.Tensor, axis: int, want_keys: bool = False):
+    """cb_retrieval_rank on the fp32 video-major score matrix (n_videos, n_captions); the rows may be a view of a padded buffer (any dim-0
+    stride >= n_captions, any 4-byte base), the last dimension is contiguous.  ``axis`` RANK_ROW_QUERIES: every row (video) is a query
+    over its columns (video -> text); RANK_COL_QUERIES: every column (caption) is a query over the rows (text -> video).  ``gt``: int32,
+    one ground-truth candidate index per query, on the same device.  -> rank int32 (n_queries,): the 1-based position of the ground truth
+    in a stable descending sort of the keys rint(1e4 * score) (0 where gt is out of range); with ``want_keys`` -> (rank, keys int32
+    (n_videos, n_captions)).  One launch, no host synchronisation."""
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError(f"retrieval_rank: expected an fp32 (n_videos, n_captions) matrix, got {scores.dtype} {tuple(scores.shape)}")
+    n_rows, n_cols = scores.shape
+    if n_cols > 1 and scores.stride(1) != 1:
+        raise ValueError("retrieval_rank: the last dimension of the score matrix must be contiguous")
+    ld = scores.stride(0) if n_rows > 1 else max(scores.stride(0), n_cols)
+    if ld < n_cols:
+        raise ValueError(f"retrieval_rank: the rows of the score matrix overlap (stride {ld} < {n_cols} columns)")
+    axis = int(axis)
+    n_q = n_cols if axis == RANK_COL_QUERIES else n_rows
+    if gt.dtype != torch.int32 or gt.dim() != 1 or gt.numel() != n_q or not gt.is_contiguous() or gt.device != scores.device:
+        raise ValueError(f"retrieval_rank: gt must be {n_q} contiguous int32 values on {scores.device}, got {gt.dtype} "
+                         f"{tuple(gt.shape)} on {gt.device}")
+    rank = torch.empty(n_q, dtype=torch.int32, device=scores.device)
+    keys = torch.empty(n_rows, n_cols, dtype=torch.int32, device=scores.device) if want_keys else None
+    _chk(_lib.get().cb_retrieval_rank(_ptr(scores), int(ld), n_rows, n_cols, axis, _ptr(gt), _ptr(rank), _ptr(keys), n_cols,
+                                      _stream(scores)), "cb_retrieval_rank")
+    return (rank, keys) if want_keys else rank
 
 
 def mc_predict(stack: torch.Tensor, n_options: int, mode: int, clip_stride: Optional[int] = None):

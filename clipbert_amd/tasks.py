@@ -221,9 +221,11 @@ def _all_sum(x: float, group=None) -> float:
 
 
 @torch.no_grad()
-def validate_retrieval(model, val_loader, eval_videos, cfg, gt_txt_id2vid_id=None, group=None) -> Dict[str, float]:
+def validate_retrieval(model, val_loader, eval_videos, cfg, gt_txt_id2vid_id=None, group=None, on_device: bool = False) -> Dict[str, float]:
     """validate of run_video_retrieval.py:224-276: mean ITM loss / accuracy over ``val_loader`` (single-clip batches as the
-    training set yields them) and the retrieval metrics of inference_retrieval over ``eval_videos``; sums over the ranks."""
+    training set yields them) and the retrieval metrics of inference_retrieval over ``eval_videos``; sums over the ranks.
+    ``on_device``: the metrics through inference_retrieval_matrix / eval_retrieval_matrix (every video against one caption list; ties in
+    the stable order) instead of the dict rows."""
     was_training = model.training
     model.eval()
     loss, n_ex, n_correct = 0.0, 0, 0
@@ -241,7 +243,11 @@ def validate_retrieval(model, val_loader, eval_videos, cfg, gt_txt_id2vid_id=Non
             pred = (logits > 0).long().view(out["loss"].shape[0], -1)          # sigmoid(x) > 0.5  <=>  x > 0
             n_correct += int((pred[:, 0] == targets.view(out["loss"].shape[0], -1)[:, 0]).sum().item())
     loss, n_ex, n_correct = _all_sum(loss, group), _all_sum(n_ex, group), _all_sum(n_correct, group)
-    _rows, metrics = inference_retrieval(model, eval_videos, cfg, gt_txt_id2vid_id, group=group)
+    if on_device:
+        matrix = inference_retrieval_matrix(model, eval_videos, cfg, group=group)
+        metrics = eval_retrieval_matrix(matrix, gt_txt_id2vid_id) if gt_txt_id2vid_id is not None else None
+    else:
+        _rows, metrics = inference_retrieval(model, eval_videos, cfg, gt_txt_id2vid_id, group=group)
     model.train(was_training)
     log = {"valid/loss": loss / max(n_ex, 1), "valid/acc": n_correct / max(n_ex, 1)}
     for kind, m in (metrics or {}).items():
@@ -479,6 +485,15 @@ def inference_retrieval_video(model, visual_inputs: torch.Tensor, text_input_ids
     ``capture``: None / False (default) = eager encoder passes.  A clipbert_amd.captured.CapturedForward = the encoder passes replay from
     its hipGraphs (one full and one remainder signature per video set; the CNN pass stays eager); True = the one kept on the model
     (created on first use), so that the graphs outlive the call.  cache_cnn=True only."""
+    scores: List[float] = []
+    for _i0, pooled in _retrieval_video_pooled(model, visual_inputs, text_input_ids, text_input_mask, cfg, cache_cnn, max_pairs_per_pass, capture):
+        scores.extend(clips.retrieval_scores(pooled))
+    return scores
+
+
+def _retrieval_video_pooled(model, visual_inputs, text_input_ids, text_input_mask, cfg, cache_cnn, max_pairs_per_pass, capture):
+    """The passes of inference_retrieval_video: yields (first caption, pooled logits (nb, C)) per text mini-batch, on the device; what
+    becomes of them -- rounded host floats, or a slice of a score-matrix row -- is the caller's."""
     if capture:
         from .captured import CapturedForward
         if not cache_cnn:
@@ -492,7 +507,6 @@ def inference_retrieval_video(model, visual_inputs: torch.Tensor, text_input_ids
     vis = visual_inputs.view(n_clips, num_frm, *visual_inputs.shape[2:])
     n_txt = text_input_ids.shape[0]
     grid = model.grid_features(vis) if cache_cnn else None          # (n_clips, T, H', W', hidden)
-    scores: List[float] = []
     for i0 in range(0, n_txt, eval_bsz):
         ids, mask = text_input_ids[i0:i0 + eval_bsz], text_input_mask[i0:i0 + eval_bsz]
         nb = ids.shape[0]
@@ -517,8 +531,7 @@ def inference_retrieval_video(model, visual_inputs: torch.Tensor, text_input_ids
         pooled = clips.aggregate_clip_logits(per_clip, pool)
         if pool == "lse":
             pooled = clips.lse_inference_logits(pooled)
-        scores.extend(clips.retrieval_scores(pooled))
-    return scores
+        yield i0, pooled
 
 
 def shard_for_rank(n_items: int, rank: int, world: int) -> range:
@@ -560,6 +573,121 @@ def inference_retrieval(model, videos, cfg, gt_txt_id2vid_id: Optional[Dict] = N
     metrics = eval_retrieval(rows, gt_txt_id2vid_id) if gt_txt_id2vid_id is not None else None
     model.train(was_training)
     return rows, metrics
+
+
+# ---- retrieval evaluation on the device (:563-734 without per-batch host traffic) ----------------------------------------------------
+class RetrievalMatrix:
+    """The scores of an evaluation as ONE video-major matrix: ``scores`` fp32 (len(vid_ids), len(txt_ids)) on the device, not rounded
+    (cb_retrieval_rank rounds to the exact integer keys); row i is video ``vid_ids[i]``, column j caption ``txt_ids[j]``."""
+
+    def __init__(self, vid_ids: List, txt_ids: List, scores: torch.Tensor):
+        assert scores.dim() == 2 and tuple(scores.shape) == (len(vid_ids), len(txt_ids)) and scores.dtype == torch.float32
+        self.vid_ids, self.txt_ids, self.scores = list(vid_ids), list(txt_ids), scores
+
+
+def merge_retrieval_parts(parts):
+    """The per-rank (vid_ids, txt_ids, fp32 numpy block (videos, captions)) triples as one: the rows concatenated in rank order, a repeated
+    vid_id dropped (the first occurrence stays, as eval_retrieval does, :578-586).  Every part must name the same captions in the same
+    order.  A pure function of its argument."""
+    parts = list(parts)
+    txt_ids = list(parts[0][1])
+    vid_ids, blocks, seen = [], [], set()
+    for rank, (vids, txts, block) in enumerate(parts):
+        if list(txts) != txt_ids:
+            raise ValueError(f"merge_retrieval_parts: rank {rank} scored other captions than rank 0 (the matrix path needs every video "
+                             "compared with the same caption list: inference_retrieval is the general path)")
+        block = np.asarray(block, dtype=np.float32).reshape(len(vids), len(txt_ids))
+        keep = []
+        for i, v in enumerate(vids):
+            if v not in seen:
+                seen.add(v)
+                keep.append(i)
+                vid_ids.append(v)
+        blocks.append(block if len(keep) == len(vids) else block[keep])
+    return vid_ids, txt_ids, np.concatenate(blocks, axis=0)
+
+
+def gather_retrieval_matrix(local: RetrievalMatrix, group=None) -> RetrievalMatrix:
+    """All ranks' rows on every rank, in rank order: ONE all_gather_object of (vid_ids, txt_ids, fp32 numpy block) per rank -- 4 bytes a
+    score where gather_retrieval_rows pickles a dict entry.  A single process returns its matrix unchanged."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return local
+    parts = [None] * dist.get_world_size(group)
+    dist.all_gather_object(parts, (local.vid_ids, local.txt_ids, local.scores.cpu().numpy()), group=group)
+    vid_ids, txt_ids, block = merge_retrieval_parts(parts)
+    return RetrievalMatrix(vid_ids, txt_ids, torch.from_numpy(block).to(local.scores.device))
+
+
+@torch.no_grad()
+def inference_retrieval_matrix(model, videos, cfg, group=None, cache_cnn: bool = True, capture=False, max_pairs_per_pass: int = 256) -> RetrievalMatrix:
+    """inference_retrieval without the dict rows: the same encoder passes, pooling and cb_retrieval_scores launches as
+    inference_retrieval_video (bit-identical fp32 scores), every mini-batch's scores written straight into its slice of the video's row of a
+    device matrix -- nothing is copied to the host inside the loop.  ``videos`` as for inference_retrieval; every video must carry the
+    same ``caption_ids`` sequence (MSRVTT 1k-A: each video against all captions), else ValueError -- inference_retrieval is the general
+    path.  A repeated vid_id is skipped, the first occurrence stays (:578-586).  Returns the matrix of all ranks (gather_retrieval_matrix)."""
+    was_training = model.training
+    model.eval()
+    vid_ids, seen, txt_ids, scores = [], set(), None, None
+    for b in videos:
+        caption_ids = list(b["caption_ids"])
+        if txt_ids is None:
+            txt_ids = caption_ids
+            capacity = max(len(videos), 1) if hasattr(videos, "__len__") else 16
+            scores = torch.empty(capacity, len(txt_ids), dtype=torch.float32, device=b["text_input_ids"].device)
+        elif caption_ids != txt_ids:
+            raise ValueError(f"inference_retrieval_matrix: video {b['vid_id']!r} carries other caption_ids than the first video; the score "
+                             "matrix needs one caption list for all videos -- use inference_retrieval, the general path")
+        if b["vid_id"] in seen:
+            continue
+        if len(vid_ids) == scores.shape[0]:                 # (an iterable without a length: the matrix grows on the device)
+            scores = torch.cat([scores, torch.empty_like(scores)])
+        row = scores[len(vid_ids)]
+        for i0, pooled in _retrieval_video_pooled(model, b["visual_inputs"], b["text_input_ids"], b["text_input_mask"], cfg, cache_cnn,
+                                                  max_pairs_per_pass, capture or None):
+            ops.retrieval_scores(pooled.float().contiguous(), out=row[i0:i0 + pooled.shape[0]])
+        seen.add(b["vid_id"])
+        vid_ids.append(b["vid_id"])
+    model.train(was_training)
+    if txt_ids is None:
+        raise ValueError("inference_retrieval_matrix: no videos")
+    return gather_retrieval_matrix(RetrievalMatrix(vid_ids, txt_ids, scores[:len(vid_ids)]), group)
+
+
+def retrieval_metrics_from_ranks(ranks) -> Dict[str, float]:
+    """get_retrieval_metric_from_bool_matrix (:519-543) from the 1-based ranks of the ground truths: the reference's expressions, float64."""
+    ranks = np.asarray(ranks, dtype=np.int64)
+    num_row = len(ranks)
+    return dict(r1=float(100 * (ranks <= 1).sum() / num_row), r5=float(100 * (ranks <= 5).sum() / num_row),
+                r10=float(100 * (ranks <= 10).sum() / num_row), medianR=float(np.median(ranks)), meanR=float(np.mean(ranks)))
+
+
+def eval_retrieval_matrix(matrix: RetrievalMatrix, gt_txt_id2vid_id: Dict) -> Dict[str, Dict[str, float]]:
+    """eval_retrieval (:563-625) on a RetrievalMatrix: the ground-truth index arrays built on the host as eval_retrieval builds them (the
+    video -> text ground truth is the inverse dict, so the LAST caption of a video wins, :618), one copy of them to the device, two
+    cb_retrieval_rank launches and one copy of both rank vectors back.  Ties: the stable order (ops.retrieval_rank)."""
+    vid_idx = {v: i for i, v in enumerate(matrix.vid_ids)}
+    txt_idx = {t: i for i, t in enumerate(matrix.txt_ids)}
+    gt_v2t = {v: t for t, v in gt_txt_id2vid_id.items()}
+    gt_cols = [vid_idx[gt_txt_id2vid_id[t]] for t in matrix.txt_ids]          # text -> video: per caption, its video's row
+    gt_rows = [txt_idx[gt_v2t[v]] for v in matrix.vid_ids]                    # video -> text: per video, its caption's column
+    gt = torch.tensor(gt_cols + gt_rows, dtype=torch.int32).to(matrix.scores.device)
+    n_txt = len(gt_cols)
+    r_t2v = ops.retrieval_rank(matrix.scores, gt[:n_txt], ops.RANK_COL_QUERIES)
+    r_v2t = ops.retrieval_rank(matrix.scores, gt[n_txt:], ops.RANK_ROW_QUERIES)
+    ranks = torch.cat([r_t2v, r_v2t]).cpu().numpy()
+    return dict(text2video=retrieval_metrics_from_ranks(ranks[:n_txt]), video2text=retrieval_metrics_from_ranks(ranks[n_txt:]))
+
+
+def retrieval_rows(matrix: RetrievalMatrix) -> List[Dict]:
+    """The reference's list of dict(vid_id, txt_id, score) (:683-688) from a RetrievalMatrix, for saving results: video-major, score =
+    key / 1e4 -- the double round(p, 4) gives.  Built only when asked for: one launch for the keys, one copy to the host."""
+    if not matrix.vid_ids or not matrix.txt_ids:
+        return []
+    no_gt = torch.full((len(matrix.vid_ids),), -1, dtype=torch.int32).to(matrix.scores.device)      # (rank 0 everywhere: only the keys are wanted)
+    _rank, keys = ops.retrieval_rank(matrix.scores, no_gt, ops.RANK_ROW_QUERIES, want_keys=True)
+    keys = keys.cpu().tolist()
+    return [dict(vid_id=v, txt_id=t, score=k / 1e4) for v, row in zip(matrix.vid_ids, keys) for t, k in zip(matrix.txt_ids, row)]
 
 
 # ---- MSRVTT multiple-choice test (run_msrvtt_mc.py:136-243) ----------------------------------------------------------------

@@ -551,6 +551,21 @@ int cb_mc_predict(const float* logits, int64_t clip_stride, int32_t n_clips, int
 enum { CB_QA_CLASSIFY = 0, CB_QA_COUNT = 1 };
 int cb_qa_predict(const float* logits, int64_t clip_stride, int32_t n_clips, int32_t n_q, int32_t C, int32_t mode, int32_t kind,
                   const void* labels, int32_t* pred, float* loss, float* pooled, void* stream);
+/* Retrieval evaluation (src/tasks/run_video_retrieval.py:546-560: torch.sort(score_matrix, dim=1, descending=True) and the position of each
+ * row's ground truth, on the scores rounded to 4 places at :687) in ONE launch per direction: no sort, no atomics, no workspace, no host
+ * synchronisation.  S: the fp32 score matrix, video-major -- row r (a video), column c (a caption) at S[r * ld + c], ld >= n_cols; a base
+ * that is only 4-byte aligned and any ld are legal.  axis CB_RANK_ROW_QUERIES: the n_rows rows are the queries and the columns their
+ * candidates (video -> text); CB_RANK_COL_QUERIES: the n_cols columns are the queries and the rows their candidates (text -> video).
+ * gt (int32, one per query): the index of the query's ground-truth candidate.  key(p) = (int32) rint((double) p * 1e4), round-half-even
+ * -- exactly the integer round(p, 4) * 1e4 of :687, the product being exact in a double --, saturated at +-2e9; a NaN gives INT32_MAX
+ * (torch.sort puts a NaN first).  rank[q] (int32, one per query) = 1 + #{c: key[q, c] > key[q, gt[q]]} + #{c < gt[q]: key[q, c] ==
+ * key[q, gt[q]]}: the 1-based position of the ground truth in a STABLE descending sort (among equal rounded scores the lower candidate
+ * index ranks first; the reference's sort leaves that order undefined).  gt[q] outside [0, candidates) gives rank[q] = 0 and nothing is
+ * read through it.  keys (int32, may be null): the key matrix, element (r, c) at keys[r * ldk + c], ldk >= n_cols.  No queries: nothing
+ * is written and nothing launched; no candidates: every rank is 0 (a memset node, no kernel); S may be null in both cases. */
+enum { CB_RANK_ROW_QUERIES = 0, CB_RANK_COL_QUERIES = 1 };
+int cb_retrieval_rank(const float* S, int64_t ld, int32_t n_rows, int32_t n_cols, int32_t axis, const int32_t* gt, int32_t* rank,
+                      int32_t* keys, int64_t ldk, void* stream);
 /* Mean of n per-example losses (the runners' loss.mean(), run_video_retrieval.py:422) and its backward
  * dx[i] = *dmean / n; `*counter += inc` on a device word (the dropout seed word a captured step advances). */
 int cb_mean_fwd(const float* x, int64_t n, float* out, void* stream);
@@ -636,7 +651,8 @@ const char* cb_last_error(void);
  * 16 = cb_mc_predict (the MSRVTT multiple-choice scoring: pooling, probability and arg-max per question; nothing else changed);
  * 17 = cb_frame_source, cb_resize_pack_u8_src, cb_resize_pack_yuv420_src, cb_resize_table_check (the raw-frame ingest from a buffer
  *      named in device memory, for captured steps; nothing else changed);
- * 18 = cb_qa_predict (the video-QA validation: pooling, answer and loss per question; nothing else changed) */
+ * 18 = cb_qa_predict (the video-QA validation: pooling, answer and loss per question; nothing else changed);
+ * 19 = cb_retrieval_rank (the retrieval evaluation: exact integer keys and the rank of every query's ground truth; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
