@@ -101,6 +101,7 @@ _SIGNATURES = {
     "cb_mlm_loss_fwd": [vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp],
     "cb_mlm_loss_bwd": [i32, vp, i64, vp, vp, vp, i64, vp, vp, i64, i32, i32, vp],
     "cb_pixel_sample": [vp, i32, i32, u64, vp, vp],
+    "cb_mlm_mask": [vp, i64, i32, vp, i32, i64, i64, i32, f32, u64, vp, vp, vp, i64, vp],
     "cb_vqa_loss_fwd": [vp, i64, vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "cb_vqa_loss_bwd": [i32, vp, i64, vp, vp, i32, vp, vp, i64, i32, i32, vp],
     "cb_colsum": [i32, vp, i64, vp, i64, i32, vp],

@@ -13,8 +13,8 @@ capture that raises has applied no part of a step -- parameters, moments and gra
 back, and the step bookkeeping it touched (lazy zero-grad flags, pending-node counts) is reset by the eager step that follows anyway; the
 signature is marked uncapturable.  From the third
 sight on: stage, ``set_learning_rates`` + ``optimizer.prepare_step()`` eagerly (fresh host-side hyper-parameters), ``graph.replay()``
-(fresh dropout masks and, with the model config's pixel_sampling = "device", a fresh pixel selection: the graph advances the device seed
-word).  The cache is LRU over ``max_graphs`` entries; an evicted signature is
+(fresh dropout masks and, with the model config's pixel_sampling = "device", a fresh pixel selection, with cfg.mlm_masking = "device" fresh
+masked-LM masks: the graph advances the device seed word).  The cache is LRU over ``max_graphs`` entries; an evicted signature is
 captured again at its next sight and its static buffers go with its graph.
 
 Nothing is silently frozen into a graph: whatever produces per-step values on the host, or takes its launch geometry from the data,
@@ -186,7 +186,7 @@ class CapturedStep(_Replayer):
 
     Signature: dtype, shape and device of every tensor of the batch and which optional keys are present; tuple(n_examples_list);
     cfg.train_n_clips, num_frm, score_agg_func, task, num_labels; model.training; for pretraining cfg.mlm_rows, mlm_capacity, use_mlm,
-    use_itm; fold_clips; pixel_sampling and pixel_random_sampling_size of the config the encoder reads.
+    use_itm, mlm_masking, mlm_probability; fold_clips; pixel_sampling and pixel_random_sampling_size of the config the encoder reads.
 
     ``pad_text_to`` (e.g. cfg.max_txt_len): text_input_ids / text_input_mask (and mlm_labels, with -100) are right-padded to that many
     columns with pad id 0 and mask 0 before the signature is taken, so that the text length of a batch stops multiplying signatures
@@ -211,7 +211,9 @@ class CapturedStep(_Replayer):
     is not on the model's device, one that is indirect already; config.
     pixel_random_sampling_size > 0 in training with pixel_sampling = "host" (numpy draws the selection per forward; "device" draws it
     inside the graph with cb_pixel_sample, seeded like the dropout masks), the labelled-rows masked-LM head without a fixed
-    cfg.mlm_capacity, non-tensor batch entries the model reads, batch tensors that are not on the model's device (a loader that left them
+    cfg.mlm_capacity (whether the batch carries the labels or cfg.mlm_masking = "device" draws them inside the step with cb_mlm_mask: the
+    count of labelled rows is then binomial, data.mlm_capacity sizes the slots; otherwise a device-masked pretraining step is captured like
+    any other and every replay masks afresh -- ``pad_text_to`` pads with the pad id, which is never labelled), non-tensor batch entries the model reads, batch tensors that are not on the model's device (a loader that left them
     on the host), and a signature whose capture raised."""
 
     RAW_TABLE = "visual_inputs.table"              # the key of a RawFrames batch's table among the staged tensors
@@ -239,7 +241,8 @@ class CapturedStep(_Replayer):
         return (entries, tuple(batch["n_examples_list"]), _get(cfg, "train_n_clips", 1), _get(cfg, "num_frm"), _get(cfg, "score_agg_func", "mean"),
                 _get(cfg, "task"), _get(cfg, "num_labels"), bool(self.model.training), _get(cfg, "mlm_rows", "labelled"), _get(cfg, "mlm_capacity"),
                 _get(cfg, "use_mlm", True), _get(cfg, "use_itm", True), bool(self.fold_clips),
-                getattr(enc_cfg, "pixel_sampling", "host") or "host", int(getattr(enc_cfg, "pixel_random_sampling_size", 0) or 0))
+                getattr(enc_cfg, "pixel_sampling", "host") or "host", int(getattr(enc_cfg, "pixel_random_sampling_size", 0) or 0),
+                _get(cfg, "mlm_masking", "host") or "host", _get(cfg, "mlm_probability", 0.15))
 
     def _describe_entry(self, v):
         from .data import RawFrames
@@ -274,7 +277,10 @@ class CapturedStep(_Replayer):
         if (self.model.training and int(getattr(enc_cfg, "pixel_random_sampling_size", 0) or 0) > 0
                 and (getattr(enc_cfg, "pixel_sampling", "host") or "host") != "device"):
             return "pixel_random_sampling_size > 0 (the selection is drawn on the host per forward; pixel_sampling = 'device' draws it in the graph)"
-        if batch.get("mlm_labels") is not None and _get(cfg, "mlm_rows", "labelled") == "labelled" and _get(cfg, "mlm_capacity") is None:
+        # (labels the batch carries, or labels tasks._pretrain_forward draws on the device: only the pretraining config has the key)
+        drawn = (_get(cfg, "mlm_masking", "host") or "host") == "device" and bool(_get(cfg, "use_mlm", True))
+        if ((batch.get("mlm_labels") is not None or drawn) and _get(cfg, "mlm_rows", "labelled") == "labelled"
+                and _get(cfg, "mlm_capacity") is None):
             return "labelled-rows masked-LM head without a fixed mlm_capacity"
         for k, v in batch.items():
             if not torch.is_tensor(v) and v is not None and k not in _SKIP_KEYS:

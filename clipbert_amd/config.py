@@ -50,7 +50,10 @@ SHARED_DEFAULTS = dict(
     e2e_weights_path=None, detectron2_weights_path=None, bert_weights_path=None, detectron2_model_cfg="", model_config=None, seed=42,
     capture_raw_frames=0)      # this project's: start_training(capture=True) replays data.RawFrames batches too (captured.CapturedStep(raw_frames=True))
 TASK_DEFAULTS = {
-    "pretraining": dict(pixel_random_sampling_size=0, pixel_sampling="host", use_itm=1, use_mlm=1),
+    # mlm_*: this project's -- "host" = the caller's collator masks the text (mask_batch_text_tokens), "device" = tasks._pretrain_forward
+    # draws the masks with cb_mlm_mask from the unmasked ids (pad id and vocabulary size come from the model config)
+    "pretraining": dict(pixel_random_sampling_size=0, pixel_sampling="host", use_itm=1, use_mlm=1, mlm_masking="host", mlm_probability=0.15,
+                        mlm_mask_token_id=103, mlm_special_ids=[101, 102]),
     "video_retrieval": dict(itm_neg_size=1, classifier="mlp", cls_hidden_scale=2, margin=0.2, loss_type="ce"),
     "video_qa": dict(classifier="mlp", cls_hidden_scale=2, loss_type="ce", task="action"),
     "vqa": dict(classifier="mlp", cls_hidden_scale=2, loss_type="bce", num_labels=3129),
@@ -63,7 +66,7 @@ def load_task_config(path: str, task: str = "video_retrieval", **overrides) -> C
     assert task in TASK_DEFAULTS, task
     cfg = Config(SHARED_DEFAULTS)
     for k, v in TASK_DEFAULTS[task].items():
-        cfg[k] = v
+        cfg[k] = list(v) if isinstance(v, list) else v
     with open(path) as fh:
         for k, v in json.load(fh).items():
             cfg[k] = v

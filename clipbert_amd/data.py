@@ -306,6 +306,20 @@ def vqa_dense_targets(ids: torch.Tensor, scores: torch.Tensor, num_labels: int) 
     return dense[:, :num_labels].contiguous()
 
 
+# ---- masked-LM slots for device-drawn masks -----------------------------------------------------------------------------------------
+def mlm_capacity(rows: int, p: float = 0.15, sigmas: float = 6.0) -> int:
+    """The slot count for cfg.mlm_capacity when the labels are drawn per step (cfg.mlm_masking = "device"): a captured step needs a fixed
+    capacity, and the count of labelled rows among ``rows`` text rows (B * Lt; special and pad rows only lower it) is binomial --
+    min(rows, ceil(rows p + sigmas sqrt(rows p (1 - p)))), rounded up to the 64 the head rounds to anyway.  A step that still overflows
+    drops the last labelled rows, visibly: model.transformer.mlm_counts[1] counts them."""
+    import math
+    rows, p = int(rows), float(p)
+    if rows < 1 or not 0.0 <= p <= 1.0 or sigmas < 0:
+        raise ValueError(f"mlm_capacity: need rows >= 1, 0 <= p <= 1 and sigmas >= 0 (rows {rows}, p {p}, sigmas {sigmas})")
+    need = min(rows, math.ceil(rows * p + sigmas * math.sqrt(rows * p * (1.0 - p))))
+    return (max(need, 1) + 63) // 64 * 64
+
+
 # ---- MSRVTT multiple-choice batches ----------------------------------------------------------------------------------------------
 def collate_mc(videos, option_ids, option_mask, question_ids, answers=None) -> Dict:
     """The batch of MSRVTTMCCollator.collate_batch (src/datasets/dataset_video_retrieval.py:328-361) from already tokenised options --

@@ -109,6 +109,7 @@ def _pick_split(mo, no, kred):
 # dropout sites -> distinct seed streams
 _SITE_EMB, _SITE_ATTN, _SITE_SELF_OUT, _SITE_OUT, _SITE_POOL, _SITE_REG = 1, 2, 3, 4, 5, 6
 _SITE_PIXEL = 7          # not a dropout: the pixel sub-sampling drawn on the device (ops.pixel_sample), a seed stream of its own
+_SITE_MLM = 8            # not a dropout: the masked-LM token masking drawn on the device (ops.mlm_mask), a seed stream of its own
 
 
 def _seed(site, layer=0, fwd=0):

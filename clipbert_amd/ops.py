@@ -861,6 +861,31 @@ def pixel_sample(lv: int, n: int, seed=0, seed_ptr=None, out=None, device=None):
     return out[:n] if out.numel() != n else out
 
 
+def mlm_mask(ids: torch.Tensor, p: float, seed=0, seed_ptr=None, special_ids=(101, 102), pad_id=0, mask_id=103, vocab_size=None,
+             out_ids=None, out_labels=None, ignore_index: int = -100):
+    """cb_mlm_mask: (ids_out, labels), both int64 of ids' shape -- the masked-LM masking of a padded (rows, Lt) id matrix, drawn on the
+    device from ``seed`` plus the device word behind ``seed_ptr`` (the dropout convention; the definition is in the header).  ``ids`` is not
+    written unless ``out_ids`` is ids itself.  ``special_ids``: at most 4 ids that are never labelled ([CLS], [SEP]); ``pad_id``: None or
+    negative = no pad token; ``vocab_size``: the range of the random words, required.  One launch on the current stream of the outputs, no
+    host sync: capturable."""
+    if vocab_size is None:
+        raise ValueError("mlm_mask: pass vocab_size= (the range of the random words)")
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.is_contiguous(), (ids.dtype, ids.shape)
+    ids_out = torch.empty_like(ids) if out_ids is None else out_ids
+    labels = torch.empty_like(ids) if out_labels is None else out_labels
+    for o in (ids_out, labels):
+        assert o.dtype == torch.int64 and o.is_contiguous() and o.shape == ids.shape and o.device == ids.device, (o.dtype, o.shape, o.device)
+    assert labels.data_ptr() != ids.data_ptr() and labels.data_ptr() != ids_out.data_ptr()
+    assert seed_ptr is None or (seed_ptr.dtype == torch.int64 and seed_ptr.numel() == 1 and seed_ptr.device == ids_out.device)
+    special = [int(x) for x in special_ids]
+    arr = (C.c_int64 * max(len(special), 1))(*special)
+    rows, lt = ids.shape
+    _chk(_lib.get().cb_mlm_mask(_ptr(ids), rows, lt, arr, len(special), -1 if pad_id is None else int(pad_id), int(mask_id), int(vocab_size),
+                                float(p), int(seed) % (1 << 64), _ptr(seed_ptr), _ptr(ids_out), _ptr(labels), ignore_index, _stream(ids_out)),
+         "cb_mlm_mask")
+    return ids_out, labels
+
+
 def elu_bn1d_fwd(x, gamma, beta, running_mean, running_var, training: bool, momentum: float = 0.1, eps: float = 1e-5, save: bool = False):
     """ELU + BatchNorm1d over the batch (ClipBertForRegression.regressor[1:3]); returns (y, save_mean, save_invstd)."""
     b, d = x.shape

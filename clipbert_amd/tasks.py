@@ -104,16 +104,57 @@ def set_learning_rates(optimizer, cfg, global_step: int, n_epoch: int = 0):
     return lr_t, lr_c
 
 
-def _pretrain_forward(model, batch: Dict, cfg) -> Dict:
+def _mlm_masking(cfg) -> str:
+    mode = _get(cfg, "mlm_masking", "host") or "host"
+    if mode not in ("host", "device"):
+        raise ValueError(f"mlm_masking must be 'host' or 'device', not {mode!r}")
+    return mode
+
+
+def _device_mlm_mask(model, ids: torch.Tensor, cfg, eval_ordinal: int):
+    """cfg.mlm_masking = "device": (masked ids, labels) of the unmasked ``ids`` (mask_batch_text_tokens of src/datasets/data_utils.py:23-70
+    drawn by cb_mlm_mask).  Training: a forward of its own in the runtime's count -- seed site _SITE_MLM at rt.forward_count, which then
+    advances, plus the device seed word, so every eager step and every replay of a captured step masks afresh.  Evaluation: the seed of
+    the ``eval_ordinal``-th batch of the pass and no seed word; no counter advances, so a validation pass repeats itself exactly."""
+    from .modeling.runtime import _SITE_MLM, _seed
+    rt, mc = model.rt, model.config
+    if model.training:
+        fwd_i = rt.forward_count
+        rt.forward_count += 1
+        seed, word = _seed(_SITE_MLM, 0, fwd_i), rt.seed_dev
+    else:
+        seed, word = _seed(_SITE_MLM, 0, int(eval_ordinal)), None
+    pad = _get(mc, "pad_token_id", 0)
+    return ops.mlm_mask(ids.contiguous(), float(_get(cfg, "mlm_probability", 0.15)), seed, word,
+                        special_ids=tuple(_get(cfg, "mlm_special_ids", (101, 102))), pad_id=0 if pad is None else pad,
+                        mask_id=int(_get(cfg, "mlm_mask_token_id", 103)), vocab_size=int(_get(mc, "vocab_size")))
+
+
+def _pretrain_forward(model, batch: Dict, cfg, eval_ordinal: int = 0) -> Dict:
     """forward_step of src/pretrain/run_pretrain.py:196-202, with the masked-LM head in the mode cfg.mlm_rows names ("labelled" unless the
-    config says "all"; cfg.mlm_capacity = fixed number of slots, None = every text row fits).  A batch without mlm_labels runs "all"."""
+    config says "all"; cfg.mlm_capacity = fixed number of slots, None = every text row fits).  A batch without mlm_labels runs "all".
+
+    cfg.mlm_masking = "device" (default "host": the caller's collator has masked the text) with cfg.use_mlm: the batch carries the UNMASKED
+    text_input_ids and no mlm_labels; both are drawn here (_device_mlm_mask; ``eval_ordinal``: the batch's place in a validation pass) and
+    go to the model as a host-masked batch would.  The output then also carries the masked ``text_input_ids`` that were used."""
+    masking = _mlm_masking(cfg)
     mini = {k: v for k, v in batch.items() if k not in ("caption_ids", "vid_id", "question_ids")}
     mini["n_examples_list"] = list(mini["n_examples_list"])
     if not _get(cfg, "use_itm", True):
         mini["itm_labels"] = None
+    drawn = masking == "device" and bool(_get(cfg, "use_mlm", True))
+    if drawn:
+        if mini.get("mlm_labels") is not None:
+            raise ValueError("mlm_masking = 'device' draws the labels from the unmasked text_input_ids: this batch carries mlm_labels, "
+                             "so its text is masked already")
+        mini["text_input_ids"], mini["mlm_labels"] = _device_mlm_mask(model, mini["text_input_ids"], cfg, eval_ordinal)
     mini["mlm_rows"] = _get(cfg, "mlm_rows", "labelled") if mini.get("mlm_labels") is not None else "all"
     mini["mlm_capacity"] = _get(cfg, "mlm_capacity")
-    return model(mini)
+    masked_ids = mini["text_input_ids"]
+    out = model(mini)
+    if drawn:
+        out["text_input_ids"] = masked_ids
+    return out
 
 
 def pretrain_loss(model, batch: Dict, cfg) -> torch.Tensor:
@@ -260,13 +301,16 @@ def validate_pretrain(model, val_loader, cfg, group=None) -> Dict[str, float]:
     """validate of src/pretrain/run_pretrain.py:205-273: masked-LM loss / accuracy per labelled token and ITM loss / accuracy per example
     over ``val_loader``, sums over the ranks.  In the labelled-rows mode the arg-max comes from ``mlm_pred``; in "all" mode it is the
     reference's own expression on ``mlm_scores`` (:233-237).  A fixed cfg.mlm_capacity that a batch overflowed is an error here, where
-    the losses are read back anyway: the dropped rows would be missing from every number."""
+    the losses are read back anyway: the dropped rows would be missing from every number.  With cfg.mlm_masking = "device" the k-th batch
+    is masked from the seed of ordinal k alone: two passes over the same loader give identical numbers (what the reference's ``is_train``
+    argument of mask_batch_text_tokens was kept for, data_utils.py:30, and never did)."""
+    _mlm_masking(cfg)                                       # (an unknown mode is refused before the model changes its mode)
     was_training = model.training
     model.eval()
     use_mlm, use_itm = _get(cfg, "use_mlm", True), _get(cfg, "use_itm", True)
     mlm_loss, n_tok, n_tok_ok, itm_loss, n_ex, n_ex_ok = 0.0, 0, 0, 0.0, 0, 0
-    for batch in val_loader:
-        out = _pretrain_forward(model, batch, cfg)
+    for k, batch in enumerate(val_loader):
+        out = _pretrain_forward(model, batch, cfg, eval_ordinal=k)      # (mlm_masking = "device": batch k of every pass draws the same masks)
         labels = out["mlm_labels"]
         if use_mlm and labels is not None:
             mlm_loss += float(out["mlm_loss"].sum().item())

@@ -445,6 +445,32 @@ int cb_mlm_loss_fwd(const float* logits, int64_t ld, const int32_t* slot_row, co
 int cb_mlm_loss_bwd(int32_t dtype, const float* logits, int64_t ld, const float* lse, const int32_t* slot_row, const int64_t* slot_label,
                     int64_t ignore_index, const float* dloss_rows, void* dlogits, int64_t ldd, int32_t cap, int32_t V, void* stream);
 
+/* ---- masked-LM token masking, drawn on the device -------------------------------------------------------------------------------------
+ * The pre-training collator masks the text of every batch on the host (mask_batch_text_tokens, src/datasets/data_utils.py:23-70: a Python
+ * loop over the rows for the special-token mask, three torch.bernoulli draws and a torch.randint).  cb_mlm_mask draws the same procedure
+ * without the host, from ONE hash per token in place of the four generators: ids int64, a padded (rows, Lt) matrix, contiguous; for
+ * element i = r * Lt + t, defined exactly (tests/mlm_mask_restatement.py restates it):
+ *   s        = seed + (seed_ptr ? *seed_ptr : 0) mod 2^64 (the convention of every dropout site: the device word advances inside a captured step);
+ *   z        = hash(s, i), the splitmix64 finaliser of the dropout masks;
+ *   eligible = ids[i] is none of special[0..n_special) and ids[i] != pad_id        (pad_id < 0: no pad token, the reference's _pad_token is None);
+ *   labelled = eligible and (z >> 40) < thr, thr = (uint32)(p * 16777216.0f)       (24 bits; p = 1 labels every eligible token);
+ *   kind     = (((z >> 24) & 0xFFFF) * 10) >> 16                                   (0..9);
+ *   word     = ((z & 0xFFFFFF) * V) >> 24                                          (0..V-1);
+ *   ids_out[i] = labelled ? (kind <= 7 ? mask_id : kind == 8 ? word : ids[i]) : ids[i];
+ *   labels[i]  = labelled ? ids[i] : ignore_index.
+ * So the special tokens ([CLS] and [SEP]: what get_special_tokens_mask flags) and the pad id are never labelled, every other token is
+ * with probability p, and a labelled token becomes [MASK] in 80 % of cases, a uniformly random word of [0, V) in 10 % and stays in 10 %.
+ * Quantisation: p is cut to a multiple of 2^-24; the three class shares are off by at most 2^-16 (6554 / 6553 / 6553 of the 65536 values
+ * of the middle field fall on each kind); a word's probability is off by at most V / 2^24 relative (each word owns floor or ceil of
+ * 2^24 / V values of the low field).  The three fields are disjoint bits of z.
+ * special: HOST array of n_special <= 4 ids, copied into the kernel arguments (may be null when n_special = 0).  The buffers need 8-byte
+ * alignment only (a view into a larger int64 buffer is legal); ids_out may be ids itself (each element is read before it is written);
+ * labels must not overlap either.  ONE elementwise launch, no host synchronisation, no scratch: capturable.  Refused with a message,
+ * launching nothing: a null ids / ids_out / labels, rows < 1, Lt < 1, n_special outside [0, 4], V outside [1, 2^24], p outside [0, 1]. */
+int cb_mlm_mask(const int64_t* ids, int64_t rows, int32_t Lt, const int64_t* special, int32_t n_special, int64_t pad_id, int64_t mask_id,
+                int32_t V, float p, uint64_t seed, const uint64_t* seed_ptr, int64_t* ids_out, int64_t* labels, int64_t ignore_index,
+                void* stream);
+
 /* ---- random pixel sub-sampling, drawn on the device ----------------------------------------------------------------------------------
  * The pre-training configuration keeps a random sorted subset of the visual tokens in every training forward
  * (get_random_sample_indices: np.random.choice(replace=False) then sort, one selection shared by the batch; src/modeling/modeling.py:15-34,
@@ -652,7 +678,8 @@ const char* cb_last_error(void);
  * 17 = cb_frame_source, cb_resize_pack_u8_src, cb_resize_pack_yuv420_src, cb_resize_table_check (the raw-frame ingest from a buffer
  *      named in device memory, for captured steps; nothing else changed);
  * 18 = cb_qa_predict (the video-QA validation: pooling, answer and loss per question; nothing else changed);
- * 19 = cb_retrieval_rank (the retrieval evaluation: exact integer keys and the rank of every query's ground truth; nothing else changed) */
+ * 19 = cb_retrieval_rank (the retrieval evaluation: exact integer keys and the rank of every query's ground truth; nothing else changed);
+ * 20 = cb_mlm_mask (the pre-training collator's masked-LM token masking drawn on the device; nothing else changed) */
 int cb_version(void);
 
 /* ---- gradient exchange (one process per GPU, RCCL over xGMI) ----------------------------------------------------
